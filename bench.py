@@ -6,7 +6,12 @@ pairs with mixed Array/Bitmap/Run containers, generated on the device (SplitMix6
 One "step" = one rbgpu_pairwise(AND) call over every pair, inputs already resident in HBM, results
 materialized in HBM (RoaringFormatSpec payloads).
 
-Secondary lines (same JSON object, key "secondary"): config 2 at the same scale for OR / XOR /
+A plain run does what the headline needs and no more: generate the inputs, warm up, time --steps steps,
+print the one JSON line (its `roofline` comes from the timed steps' own kernel events).  --dump-outputs DIR
+also writes the last timed step's result as DIR/<name>.npy (dump_outputs).  Everything below that takes
+runs of its own — the CPU baselines and the secondary lines — is behind --full.
+
+Secondary lines (--full; same JSON object, key "secondary"): config 2 at the same scale for OR / XOR /
 ANDNOT; config 1 (census1881, 4 ops); config 5 (BSI RANGE, 64 x 100M); config 3 (FastAggregation.or
 of 1024 dense bitmaps); config 4 (FastAggregation.and / .xor of 4096 run-heavy bitmaps).  Each
 carries `roofline` (its dominant kernel's algorithmic bytes / HIP-event duration on the library
@@ -174,12 +179,24 @@ def parse():
                    choices=["pairwise_and", "pairwise_or", "pairwise_xor", "pairwise_andnot", "wide_or",
                             "wide_and_runs", "wide_xor_runs", "bsi_range"])
     p.add_argument("--wide-bitmaps", type=int, default=0, help="bitmaps of a wide workload (0: the config's)")
-    p.add_argument("--secondary", default="all",
-                   help="comma list of secondary lines: pairwise_ops,census,bsi_range,wide_or,wide_and_runs,"
-                        "wide_xor_runs; 'all' or 'none'")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="headline CPU baseline budget")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the CPU baselines and the secondary lines (runs of their own)")
+    p.add_argument("--secondary", default=None,
+                   help="with --full, comma list of secondary lines: pairwise_async,pairwise_ops,census,bsi_range,"
+                        "wide_or,wide_and_runs,wide_xor_runs; 'all' (the default with --full) or 'none'")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="headline CPU baseline budget (with --full)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's result as DIR/<name>.npy (float64)")
+    args = p.parse_args()
+    if args.full:
+        args.secondary = args.secondary or "all"
+    else:  # a plain run: set up, warm up, time the steps, print the line
+        if args.secondary not in (None, "none"):
+            p.error("--secondary lines are runs of their own: they need --full")
+        args.secondary = "none"
+        args.no_cpu_baseline = True
+    return args
 
 
 SECONDARY_ALL = ["pairwise_async", "pairwise_ops", "census", "bsi_range", "wide_or", "wide_and_runs", "wide_xor_runs"]
@@ -309,6 +326,93 @@ def step_spread(D):
             "spread_pct": round(100.0 * (v[-1] - v[0]) / float(np.median(v)), 2)}
 
 
+class LastResult:
+    """Every step frees its result, except that with --dump-outputs the last timed step's stays open
+    for dump_outputs (self.r)."""
+
+    def __init__(self, keep: bool, calls: int):
+        self.keep, self.left, self.r = keep, calls, None
+
+    def done(self, r):
+        self.left -= 1
+        if self.keep and self.left == 0:
+            self.r = r
+        else:
+            r.close()
+
+
+DUMP_SEED = 20240229
+DUMP_MAX_BYTES = 64 << 20
+DUMP_BITMAPS = 1 << 20        # per-bitmap figures: every bitmap up to this many, else a seeded sample
+DUMP_SAMPLE = 256             # bitmaps whose containers and values are written
+DUMP_CONTAINERS = 1 << 19     # container records, all sampled bitmaps together
+DUMP_VALUES = 3 << 20         # values, all sampled bitmaps together
+DUMP_VALUE_CONTAINERS = 16    # containers per sampled bitmap whose values are written
+
+
+def dump_outputs(dirpath, r):
+    """--dump-outputs: the result set `r` of the last timed step (what the caller of the timed path
+    holds) as float64 .npy files, at most DUMP_MAX_BYTES in all.  Per bitmap: cardinality and
+    serialized size (every bitmap, or a seeded sample of a larger batch, listed in bitmap_index).  For
+    a seeded sample of the bitmaps: every container's key, type and cardinality (the type decisions),
+    and the values of up to DUMP_VALUE_CONTAINERS of its containers.  The sample depends only on the
+    seed and the batch's shape, so two builds write the same entries."""
+    os.makedirs(dirpath, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    n = len(r)
+    which = np.arange(n) if n <= DUMP_BITMAPS else np.sort(rng.choice(n, DUMP_BITMAPS, replace=False))
+    out = {"bitmap_index": which, "cardinalities": r.cardinalities()[which],
+           "serialized_sizes": r.serialized_sizes()[which]}
+    sample = np.sort(rng.choice(n, min(n, DUMP_SAMPLE), replace=False)) if n else np.zeros(0, np.int64)
+    max_conts, max_vals = DUMP_CONTAINERS // max(len(sample), 1), DUMP_VALUES // max(len(sample), 1)
+    keys, types, cards, vals, cbegin, vbegin = [], [], [], [], [0], [0]
+    for b in sample:
+        h = r.download(int(b), 1)
+        nc = min(h.n_containers, max_conts)
+        keys.append(h.key[:nc])
+        types.append(h.type[:nc])
+        cards.append(h.card[:nc])
+        cbegin.append(cbegin[-1] + nc)
+        pick = np.arange(nc) if nc <= DUMP_VALUE_CONTAINERS else \
+            np.sort(np.random.default_rng(DUMP_SEED + int(b)).choice(nc, DUMP_VALUE_CONTAINERS, replace=False))
+        one = container_values(h, pick)[:max_vals]
+        vals.append(one)
+        vbegin.append(vbegin[-1] + len(one))
+
+    def cat(xs):
+        return np.concatenate(xs) if xs else np.zeros(0)
+
+    out.update({"sample_bitmaps": sample, "sample_container_begin": np.array(cbegin),
+                "sample_container_keys": cat(keys), "sample_container_types": cat(types),
+                "sample_container_cardinalities": cat(cards), "sample_value_begin": np.array(vbegin),
+                "sample_values": cat(vals)})
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= DUMP_MAX_BYTES, total
+    for k, v in out.items():
+        np.save(os.path.join(dirpath, k + ".npy"), v)
+    return {"dir": dirpath, "bytes": int(total), "arrays": sorted(out)}
+
+
+def container_values(h, pick):
+    """uint32 values (ascending) of the containers `pick` of a one-bitmap HostSoA."""
+    from roaringbitmap_amd import _lib as L
+    out = []
+    for i in pick:
+        i = int(i)
+        p, t, hi = h.container_payload(i), int(h.type[i]), np.uint32(int(h.key[i]) << 16)
+        if t == L.ARRAY:
+            low = p.view(np.uint16).astype(np.uint32)
+        elif t == L.BITMAP:
+            low = np.nonzero(np.unpackbits(p, bitorder="little"))[0].astype(np.uint32)
+        else:  # (start, length - 1) runs
+            rl = p.view(np.uint16).reshape(-1, 2).astype(np.int64)
+            n = rl[:, 1] + 1
+            low = (np.repeat(rl[:, 0] - (np.cumsum(n) - n), n) + np.arange(int(n.sum()))).astype(np.uint32)
+        out.append(low | hi)
+    return np.concatenate(out) if out else np.zeros(0, np.uint32)
+
+
 def roofline(main_name, k_ms, k_bytes, traffic, D, extra=None):
     k_ms_max = D.reduce([k_ms], "max")[0]
     achieved = k_bytes / (k_ms_max * 1e-3) / 1e9 if k_ms_max > 0 else 0.0
@@ -322,12 +426,13 @@ def roofline(main_name, k_ms, k_bytes, traffic, D, extra=None):
 
 
 # ------------------------------------------------------------------------------- config 2
-def pairwise_line(D, ctx, rb, a, b, op, steps, warmup, npairs):
+def pairwise_line(D, ctx, rb, a, b, op, steps, warmup, npairs, last_r=None):
     """Config 2 for one op: every rank runs its own npairs pairs (weak scaling); per step the
     ShardedPairwise exchange (all_reduce of result cardinality / containers / bytes) at N > 1."""
     from roaringbitmap_amd.sharding import PairShardResult, ShardedPairwise
     comm = D.comm
     sp = ShardedPairwise(D.td, D.rank, D.world, D.device) if D.td is not None and comm is None else None
+    last_r = last_r or LastResult(False, 0)
 
     def step():
         r = ctx.pairwise(op, a, b)
@@ -340,7 +445,7 @@ def pairwise_line(D, ctx, rb, a, b, op, steps, warmup, npairs):
                 glob = PairShardResult(None, (0, npairs), int(g[0]), int(g[1]), int(g[2]))
             else:
                 glob = sp.finish(None, (0, npairs), st.result_cardinality, st.result_containers, payload)
-        r.close()
+        last_r.done(r)
         return st, glob
 
     from roaringbitmap_amd.engine import stats_dict
@@ -522,7 +627,7 @@ BSI_NSLICES, BSI_NROWS = 64, 100_000_000
 BSI_LO, BSI_HI = 0x3A00_0000_0000_0000, 0xB100_0000_0000_0000  # a mid-range window: no min/max shortcut
 
 
-def run_bsi(args, D, ctx, rb, steps=5, warmup=2):
+def run_bsi(args, D, ctx, rb, steps=5, warmup=2, last_r=None):
     """Config 5: Roaring64BitmapSliceIndex.compare(RANGE, lo, hi, null) over 64 slices x 100M rows
     (runOptimize'd BSI, random value bits) — one fused pass per high key for both O'Neil chains.
     At N > 1 rank r holds and answers its high-key range (ShardedBsi; strong scaling)."""
@@ -536,6 +641,7 @@ def run_bsi(args, D, ctx, rb, steps=5, warmup=2):
     vmin, vmax = 0, (1 << BSI_NSLICES) - 1
     comm = D.comm
     sb = ShardedBsi(D.td, D.rank, D.world, D.device) if D.td is not None and comm is None else None
+    last_r = last_r or LastResult(False, 0)
 
     def step():
         if comm is not None:  # rbgpu_bsi_compare_sharded: local key range + summary all-gather in librbgpu
@@ -545,7 +651,7 @@ def run_bsi(args, D, ctx, rb, steps=5, warmup=2):
             r = ctx.bsi_compare(rb.BSI_RANGE, d, BSI_LO, BSI_HI, vmin, vmax, key_range=kr)
             st = ctx.stats_raw()  # the struct; converted to a dict after the timed loop
             card = sb.finish(r, kr, r.summaries()[0]).cardinality if sb is not None else None
-        r.close()
+        last_r.done(r)
         return st, card
 
     from roaringbitmap_amd.engine import stats_dict
@@ -644,7 +750,7 @@ WIDE_SETUP_PARTS = {"FAST_OR": ("dense_check",), "FAST_AND": ("dense_check",),
 WIDE_META_BYTES = {"FAST_XOR": 4, "FAST_AND": 10}
 
 
-def run_wide(args, name, D, ctx, rb, nbitmaps, steps, warmup, a=None):
+def run_wide(args, name, D, ctx, rb, nbitmaps, steps, warmup, a=None, last_r=None):
     """Key-range-sharded wide aggregation: rank r generates and aggregates keys [lo_r, hi_r) of the
     one global dataset (strong scaling: total work fixed), then the RCCL exchange of the shard
     summaries (roaringbitmap_amd.sharding).  The synthetic data is uniform over keys, so equal key
@@ -659,6 +765,7 @@ def run_wide(args, name, D, ctx, rb, nbitmaps, steps, warmup, a=None):
     sem = getattr(rb, sem_name)
     comm = D.comm
     sw = ShardedWide(D.td, D.rank, D.world, device=D.device) if D.td is not None and comm is None else None
+    last_r = last_r or LastResult(False, 0)
 
     def step():
         if comm is not None:  # rbgpu_wide_sharded: local key range + summary all-gather in librbgpu
@@ -673,7 +780,7 @@ def run_wide(args, name, D, ctx, rb, nbitmaps, steps, warmup, a=None):
             res = sw.aggregate(ctx, sem, a, (lo, hi))
             r = res.local
             st = ctx.stats()
-        r.close()
+        last_r.done(r)
         return st, res
 
     el, sts = timed(D, ctx, steps, warmup, step)
@@ -770,15 +877,22 @@ def main():
     if D.comm_error:
         line["comm_fallback"] = D.comm_error
     secondary = {}
+    last_r = LastResult(bool(args.dump_outputs) and D.rank == 0, args.warmup + args.steps)
+
+    def dump_last():  # --dump-outputs: rank 0's result of the last timed step, then freed like every other
+        if last_r.r is not None:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, last_r.r)
+            last_r.r.close()
 
     if args.workload in WIDE_WORKLOADS or args.workload == "bsi_range":
         if args.workload == "bsi_range":
-            w = run_bsi(args, D, ctx, rb, args.steps, args.warmup)
+            w = run_bsi(args, D, ctx, rb, args.steps, args.warmup, last_r=last_r)
         else:
             nb = args.wide_bitmaps or WIDE_WORKLOADS[args.workload][2]
-            w = run_wide(args, args.workload, D, ctx, rb, nb, args.steps, args.warmup)
-            if D.world == 1 and not args.no_cpu_baseline:
-                w["cpu_baseline"] = wide_cpu_baseline(ctx, rb, args.workload, args.cpu_seconds / 2)
+            w = run_wide(args, args.workload, D, ctx, rb, nb, args.steps, args.warmup, last_r=last_r)
+        dump_last()
+        if args.workload in WIDE_WORKLOADS and D.world == 1 and not args.no_cpu_baseline:
+            w["cpu_baseline"] = wide_cpu_baseline(ctx, rb, args.workload, args.cpu_seconds / 2)
         line.update({"value": w["value"], "unit": "GB/s", "ms_per_step": w["ms_per_step"], "step_ms": w["step_ms"],
                      "scaling": "strong",
                      "config": {k: v for k, v in w.items() if k not in ("value", "roofline", "ms_per_step", "step_ms",
@@ -795,7 +909,8 @@ def main():
         args.workload]
     a, b = ctx.generate(rb.WL_FILTER_POSTING, args.pairs, seed=seed)
     ctx.synchronize()
-    h = pairwise_line(D, ctx, rb, a, b, op, args.steps, args.warmup, args.pairs)
+    h = pairwise_line(D, ctx, rb, a, b, op, args.steps, args.warmup, args.pairs, last_r=last_r)
+    dump_last()
     line.update({"value": h["value"], "unit": "GB/s", "ms_per_step": h["ms_per_step"], "step_ms": h["step_ms"],
                  "scaling": "weak",
                  "config": {"workload": h["workload"], "units_per_gpu": args.pairs, "unit": "pairs",
