@@ -15,7 +15,11 @@ OBJ = os.path.join(HERE, "build_obj")
 ARCH = os.environ.get("RBGPU_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", os.path.join(ROOT, "include"),
-         "-Wall", "-Wno-unused-function"]
+         "-Wall", "-Wno-unused-function",
+         # remarks only (no effect on code generation): each kernel's registers, spills, scratch and occupancy,
+         # kept beside the object as <source>.resources.txt (tests/test_kernel_resources.py reads it)
+         "-Rpass-analysis=kernel-resource-usage"]
+RESOURCES_SUFFIX = ".resources.txt"
 
 
 def _newer(src_list, target):
@@ -36,7 +40,7 @@ def build(verbose: bool = False, defines=(), out: str = OUT, obj: str = OBJ) -> 
     for s in sources:
         o = os.path.join(obj, os.path.basename(s) + ".o")
         objs.append(o)
-        if _newer([s] + headers, o):
+        if _newer([s] + headers, o) or not os.path.exists(o[:-len(".o")] + RESOURCES_SUFFIX):  # no object without its record
             dflags = [f"-D{d}" for d in defines]
             cmd = [HIPCC] + FLAGS + dflags + ["-c", s, "-o", o]
             if s.endswith(".cpp"):
@@ -49,6 +53,9 @@ def build(verbose: bool = False, defines=(), out: str = OUT, obj: str = OBJ) -> 
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"compile failed: {' '.join(cmd)}\n{r.stderr}")
+        if "-c" in cmd:  # the compile's remarks (and warnings) beside its object
+            with open(cmd[-1][:-len(".o")] + RESOURCES_SUFFIX, "w") as f:
+                f.write(r.stderr)
         return r.stderr
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:

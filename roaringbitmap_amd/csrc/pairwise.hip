@@ -777,10 +777,6 @@ __device__ __forceinline__ RecU load_rec(const TaskRec *r) {
 //           the left; ArrayContainer.and/andNot :184-271, BitmapContainer.and(Array) :162-172,
 //           RunContainer.and(Array) :305-336): P = F, Q = the other operand X, staged in LDS;
 //   kHeavy  everything else: P = A, Q = B as 65536-bit register bitmaps.
-#ifndef RBG_HEAVY_NOPF
-#define RBG_HEAVY_NOPF 0 // study: register-path tasks without the one-task prefetch, at 128 VGPRs, so three
-                         // light waves fit beside each heavy one on a SIMD
-#endif
 #ifndef RBG_HEAVY_MERGE
 #define RBG_HEAVY_MERGE 0 // study builds: 1 merges OR / XOR of two small Arrays here (slower: DESIGN.md §7 r06)
 #endif
@@ -789,10 +785,9 @@ __device__ __forceinline__ RecU load_rec(const TaskRec *r) {
 #endif
 constexpr int kLightWaves = 4; // waves per SIMD of the copy + filter kernel (128 VGPRs)
 #ifndef RBG_HEAVY_WAVES
-#define RBG_HEAVY_WAVES (RBG_HEAVY_NOPF ? 4 : 2)
+#define RBG_HEAVY_WAVES 2
 #endif
 constexpr int kHeavyWaves = RBG_HEAVY_WAVES; // waves per SIMD the register-path kernel is allocated for
-constexpr bool kHeavyPrefetch = !RBG_HEAVY_NOPF;    // the next task's payloads in flight during this one's emission
 #ifndef RBG_STUDY
 #define RBG_STUDY 0 // study builds: per-phase s_memtime totals of a few light / heavy waves (printf)
 #endif
@@ -1002,24 +997,31 @@ constexpr uint32_t kQueueStride = 16; // counters 128 B apart
 // the API reserves 32 counters (4 KiB): 16 for the light tasks' queue, 16 for the heavy tasks'
 static_assert(kQueueStripes >= 1 && kQueueStripes <= 16, "two queues of at most 16 counters");
 constexpr uint32_t kHeavyQueueOffset = 16 * kQueueStride;
-// Next chunk [s, e) of the wave's current sub-range, moving to the following sub-ranges as they run
-// dry; s = n when every sub-range is exhausted.  One vector atomic by lane 0 per try, broadcast.
+// Chunks [s, e) of the wave's current sub-range, moving to the following sub-ranges as they run dry; s = n
+// when every sub-range is exhausted.  One vector atomic by lane 0 per try.  A claim is in two halves so that
+// the atomic's round trip (1-3 us under streaming load) passes behind the tasks of the chunk before:
+// claim_issue sends the atomic and leaves the ticket in lane 0's VGPR, claim_take reads it (the only wait)
+// when that chunk is needed.  Tickets are kept as 32 bits: a sub-range holds under 2^29 tasks (task ids are
+// u32) and every wave overshoots its end by at most one chunk per launch.
 struct Chunk {
   uint64_t s, e;
 };
-__device__ __forceinline__ Chunk claim_chunk(unsigned long long *queue, uint64_t n, uint32_t &k, uint32_t &tried,
-                                             int lane) {
+__device__ __forceinline__ uint32_t claim_issue(unsigned long long *queue, uint32_t k, int lane) {
+  unsigned long long v = 0;
+  if (lane == 0)
+    v = __hip_atomic_fetch_add(queue + k * kQueueStride, (unsigned long long)kQueueChunk, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+  return (uint32_t)v;
+}
+// `ticket`: claim_issue's of sub-range k; when that sub-range has run dry the following ones are tried at once
+__device__ __forceinline__ Chunk claim_take(unsigned long long *queue, uint64_t n, uint32_t &k, uint32_t &tried,
+                                            uint32_t ticket, int lane) {
   while (tried < kQueueStripes) {
     const uint64_t lo = n * k / kQueueStripes, hi = n * (k + 1) / kQueueStripes;
-    unsigned long long v = 0;
-    if (lane == 0)
-      v = __hip_atomic_fetch_add(queue + k * kQueueStride, (unsigned long long)kQueueChunk, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-    const uint64_t st = lo + pack2(__builtin_amdgcn_readfirstlane((uint32_t)v),
-                                   __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32)));
+    const uint64_t st = lo + __builtin_amdgcn_readfirstlane(ticket);
     if (st < hi) return Chunk{st, min(st + kQueueChunk, hi)};
     k = (k + 1) % kQueueStripes;
-    ++tried;
+    if (++tried < kQueueStripes) ticket = claim_issue(queue, k, lane);
   }
   return Chunk{n, n};
 }
@@ -1047,18 +1049,16 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // static schedule (queue == nullptr): wave w takes tasks w, w + stride, ...; dynamic: chunks of
   // kQueueChunk consecutive tasks from a device counter shared by every launch on it (the
-  // concurrent phase's second light launch fills the CUs the heavy kernel leaves), the next chunk
-  // claimed one chunk ahead so the atomic's latency is hidden
+  // concurrent phase's second light launch fills the CUs the heavy kernel leaves), the next chunk's
+  // ticket drawn when a chunk starts and read when it ends, so the atomic's latency is hidden
   const uint64_t stride = (uint64_t)gridDim.x * 4;
-  uint64_t g = (uint64_t)blockIdx.x * 4 + wv, cend = 0, nxt = 0, nend = 0;
-  uint32_t qk = (uint32_t)(g % kQueueStripes), qtried = 0;
+  uint64_t g = (uint64_t)blockIdx.x * 4 + wv, cend = 0;
+  uint32_t qk = (uint32_t)(g % kQueueStripes), qtried = 0, ticket = 0;
   if (queue) {
-    const Chunk c0 = claim_chunk(queue, n, qk, qtried, lane);
+    const Chunk c0 = claim_take(queue, n, qk, qtried, claim_issue(queue, qk, lane), lane);
     g = c0.s;
     cend = c0.e;
-    const Chunk c1 = claim_chunk(queue, n, qk, qtried, lane);
-    nxt = c1.s;
-    nend = c1.e;
+    if (qtried < kQueueStripes) ticket = claim_issue(queue, qk, lane);
   }
   if (g >= n) return;
   uint32_t *s = lds[wv];
@@ -1075,18 +1075,20 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
 #define RBG_LT(x)
 #define RBG_HT(x)
 #endif
-  load_chunks(pq, tc.pp, tc.bigp ? 16u : tc.pbytes, lane);
-  if (ROLE == kRoleHeavy && !kHeavyPrefetch) {
-  } else if (tc.kind == kCopy || tc.bigq) load_chunks(qq, tc.pp, 16, lane);
+  // Q before P, the order the loop issues them in: the waits the compiler counts for the loop's first loads
+  // take the smaller of the two orders, and P last here made each of them a full drain
+  if (tc.kind == kCopy || tc.bigq) load_chunks(qq, tc.pp, 16, lane);
   else load_chunks(qq, tc.pq, tc.qbytes, lane);
+  load_chunks(pq, tc.pp, tc.bigp ? 16u : tc.pbytes, lane);
   while (true) {
     uint64_t gn = g + stride;
-    bool new_chunk = false;
     if (queue) {
       gn = g + 1;
-      if (gn >= cend) { // wave-uniform branch: only here is the claimed chunk waited for
-        gn = nxt;
-        new_chunk = true;
+      if (gn >= cend) { // wave-uniform branch: only here is the ticket drawn a chunk ago waited for
+        const Chunk c1 = claim_take(queue, n, qk, qtried, ticket, lane);
+        gn = c1.s;
+        cend = c1.e;
+        if (qtried < kQueueStripes) ticket = claim_issue(queue, qk, lane);
       }
     }
     const bool has_next = gn < n;
@@ -1103,9 +1105,8 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
     if (ROLE == kRoleHeavy && OP == RB_AND && tc.tp == kRun && tc.tq == kRun && !tc.bigp &&
         !tc.bigq && ((tc.rp + 3) & ~3u) + tc.rq <= 2048u) {
       int r = 0;
-      if (!kHeavyPrefetch) load_chunks(qq, tc.pq, tc.qbytes, lane);
       done = and_runs_intervals<CARD_ONLY>(pq, qq, tc.rp, tc.rq, s, dst, lane, c, r);
-      if (done && kHeavyPrefetch) {
+      if (done) {
         ty = c == 0 ? kEmpty : CARD_ONLY ? kArray : kRun;
         nr = ty == kRun ? (uint32_t)r : 0u;
         __builtin_amdgcn_sched_barrier(0);
@@ -1114,9 +1115,6 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
           load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
         }
         load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
-      } else if (done) {
-        ty = c == 0 ? kEmpty : CARD_ONLY ? kArray : kRun;
-        nr = ty == kRun ? (uint32_t)r : 0u;
       }
     }
     if (ROLE == kRoleHeavy && RBG_HEAVY_MERGE && !done && (OP == RB_OR || OP == RB_XOR) && !tm.lazy &&
@@ -1127,13 +1125,11 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       //      kernel the long pole: profiles/r05/merge).
       merge_stage(pq, tc.cp, qq, tc.cq, s, lane);
       __builtin_amdgcn_sched_barrier(0);
-      if (kHeavyPrefetch) { // the staged payloads' registers are free: the next task's loads go out now
-        {
-          const bool real = has_next && !tn.bigq;
-          load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
-        }
-        load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
+      { // the staged payloads' registers are free: the next task's loads go out now
+        const bool real = has_next && !tn.bigq;
+        load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
       }
+      load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
       c = (int)merge_run<OP, !CARD_ONLY>(s, tc.cp, tc.cq, reinterpret_cast<uint16_t *>(dst), lane);
       ty = CARD_ONLY ? (c ? kArray : kEmpty) : (c || (OP == RB_XOR && tm.keep_empty)) ? kArray : kEmpty;
       nr = 0;
@@ -1167,11 +1163,6 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
         lds_read_words(s, w, lane);
         wave_lds_sync();
       }
-      // without prefetch Q is loaded only now, once P's registers are free (P and Q are never live
-      // together: the wave fits 128 VGPRs)
-      if (!kHeavyPrefetch && !(OP == RB_AND && tc.tp == kRun && tc.tq == kRun && !tc.bigp && !tc.bigq &&
-                               ((tc.rp + 3) & ~3u) + tc.rq <= 2048u))
-        load_chunks(qq, tc.bigq ? tc.pp : tc.pq, tc.bigq ? 16u : tc.qbytes, lane);
       if (bitmap_payload(tc.tq, tc.cq)) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -1202,13 +1193,11 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       //      scheduler from hoisting these loads above the consumption of the current ones)
       RBG_HT(lt2 = __builtin_amdgcn_s_memtime(); lt_acc[1] += lt2 - lt1);
       __builtin_amdgcn_sched_barrier(0);
-      if (kHeavyPrefetch) {
-        {
-          const bool real = has_next && !tn.bigq;
-          load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
-        }
-        load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
+      {
+        const bool real = has_next && !tn.bigq;
+        load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
       }
+      load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
       const int ta = tc.tp, tb = tc.tq;
       const bool lazy = OP == RB_OR && tm.lazy;
       const bool eff = eff_rule<OP>(ta, tb, tc.cp, tc.cq);
@@ -1237,15 +1226,21 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
     } else if (ROLE != kRoleHeavy) {
       // ---- phase 1: stage X (filter; kBits: the other operand) or store the clone (copy)
       if (tc.kind == kFilter || tc.kind == kBits) {
-        if (tc.bigq) stage_big_runs(tc.pq, tc.rq, s, lane); // only a Run payload exceeds 8 KiB
-        else stage_from_chunks(tc.tq, qq, tc.cq, tc.rq, s, lane);
+        if (tc.bigq) stage_big_runs(tc.pq, tc.rq, s, fresh(lane)); // only a Run payload exceeds 8 KiB
+        else stage_from_chunks(tc.tq, qq, tc.cq, tc.rq, s, fresh(lane));
       } else if (!CARD_ONLY) {
-        if (tc.bigp) copy_payload(tc.pp, dst, tc.pbytes, lane);
-        else store_chunks(pq, dst, tc.pbytes, lane);
+        if (tc.bigp) {
+          copy_payload(tc.pp, dst, tc.pbytes, fresh(lane), qq); // Q's registers: a copy has no Q
+          // The round's loads are waited for under each row's exec branch, so on a path that skips a row's
+          // store the compiler counts that load as still pending; the row's registers are temporaries of the
+          // staging and of the filter, which then start with a full drain on EVERY task.  A full wait here,
+          // on this rare path only, ends that (not a counted wait: everything the copy issued is waited for).
+          __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
+        } else store_chunks(pq, dst, tc.pbytes, fresh(lane));
       }
       {
         const bool real = has_next && tn.kind != kCopy && !tn.bigq;
-        load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
+        load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, fresh(lane));
       }
       RBG_LT(lt2 = __builtin_amdgcn_s_memtime(); lt_acc[tc.kind == kFilter ? 1 + (tc.tq == kBitmap ? 0 : tc.tq == kArray ? 1 : 2) : 4] += lt2 - lt1);
       // ---- phase 2: filter F against the staged X, in value order (adjacent lanes, adjacent values)
@@ -1255,8 +1250,8 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       if (tc.kind == kFilter) {
         uint16_t *o = CARD_ONLY ? nullptr : reinterpret_cast<uint16_t *>(dst);
         uint4 *tb = tbuf[ROLE == kRoleLight ? wv : 0];
-        c = OP == RB_ANDNOT ? filter_rows_linear<true, !CARD_ONLY>(pq, (int)tc.cp, s, ob, tb, o, lane)
-                            : filter_rows_linear<false, !CARD_ONLY>(pq, (int)tc.cp, s, ob, tb, o, lane);
+        c = OP == RB_ANDNOT ? filter_rows_linear<true, !CARD_ONLY>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane))
+                            : filter_rows_linear<false, !CARD_ONLY>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane));
         ty = c ? kArray : kEmpty;
       } else if (tc.kind == kBits) {
         // ---- OR into the large Bitmap P (bits_task): the rows ORed and counted first, then stored — as the
@@ -1292,7 +1287,7 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
         nr = tc.rp;
       }
       RBG_LT(lt_acc[5] += __builtin_amdgcn_s_memtime() - lt2);
-      load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
+      load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, fresh(lane));
     }
     wave_lds_sync(); // the next task restages the same LDS image
     if (lane == 0) {
@@ -1302,17 +1297,9 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
     RBG_LT(lt_acc[6] += __builtin_amdgcn_s_memtime() - lt0; ++lt_acc[7]);
     RBG_HT(lt_acc[6] += __builtin_amdgcn_s_memtime() - lt0; ++lt_acc[7]);
     if (!has_next) break;
-    if (new_chunk) {
-      cend = nend;
-      const Chunk c1 = claim_chunk(queue, n, qk, qtried, lane);
-      nxt = c1.s;
-      nend = c1.e;
-    }
     g = gn;
     cur = nx;
     tc = tn;
-    if (ROLE == kRoleHeavy && !kHeavyPrefetch) // this task's first payload, loaded only now
-      load_chunks(pq, tc.pp, tc.bigp ? 16u : tc.pbytes, lane);
   }
 #if RBG_STUDY
   if (ROLE == kRoleLight && lane == 0 && wv == 0 && blockIdx.x % 97 == 0)
@@ -1615,7 +1602,7 @@ static void launch_op(bool card_only, const uint8_t *pa, const uint8_t *pb, cons
   if (card_only) launch_tasks<OP, true, kRoleHeavy>(pa, pb, heavy, nh, out, tm, st);
   else launch_tasks<OP, false, kRoleHeavy>(pa, pb, heavy, nh, out, tm, st);
 }
-constexpr unsigned kConcLightPerCu = RBG_HEAVY_NOPF ? 3 : 2; // light blocks per CU beside the heavy kernel (2 x 128 VGPRs per SIMD)
+constexpr unsigned kConcLightPerCu = 2; // light blocks per CU beside the heavy kernel (2 x 128 VGPRs per SIMD)
 constexpr unsigned kConcHeavyPerCu = 1; // heavy blocks per CU (256 VGPRs per SIMD)
 template <int OP>
 static void launch_op_concurrent(bool card_only, const uint8_t *pa, const uint8_t *pb, const TaskRec *light,

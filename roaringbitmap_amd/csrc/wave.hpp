@@ -25,6 +25,14 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+// The same value in a register of its own that the compiler neither hoists nor shares: lane-derived offsets
+// and chunk indices (lane * 16 + 1024 i, lane + 64 i, ...) computed from it are rebuilt where they are used
+// (one VALU each, or an instruction offset) instead of being held as loop invariants — in the copy + filter
+// kernel those took ~30 of its 128 VGPRs across the whole task loop and pushed payload rows into scratch.
+__device__ __forceinline__ int fresh(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
 
 // XCD-aware block order (cdna_hip_programming.md §5 T1): blocks b, b+8, b+16, ... share an XCD's L2,
 // so they get consecutive logical indices — neighbouring keys of a wide aggregation then read the
@@ -837,6 +845,15 @@ __device__ __forceinline__ void copy_payload(const uint8_t *src, uint8_t *dst, u
     uint4 q[8];
     load_chunks(q, src + o, nb, lane);
     store_chunks(q, dst + o, nb, lane);
+  }
+}
+// The same with the round's registers lent by a caller that holds a payload buffer it no longer needs, and
+// nothing lane-derived kept across rounds (fresh); a container payload's size fits 32 bits.
+__device__ __forceinline__ void copy_payload(const uint8_t *src, uint8_t *dst, uint32_t bytes, int lane, uint4 (&q)[8]) {
+  for (uint32_t o = 0; o < bytes; o += kBitmapBytes) {
+    const uint32_t nb = min(bytes - o, (uint32_t)kBitmapBytes);
+    load_chunks(q, src + o, nb, fresh(lane));
+    store_chunks(q, dst + o, nb, fresh(lane));
   }
 }
 
