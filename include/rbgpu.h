@@ -307,6 +307,29 @@ int rbgpu_bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t sta
 int rbgpu_bsi_compare_keys(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start_or_value, uint64_t end,
                            uint64_t min_value, uint64_t max_value, const rbgpu_set *found, uint32_t key_lo,
                            uint32_t key_hi, rbgpu_set **out);
+/* The aggregate half of a BSI query, on the device.  `bsi` as for rbgpu_bsi_compare (1..65 bitmaps: at most
+ * 64 slices, then ebM); `found` is a one-bitmap set; key ranges obey key_lo <= key_hi <= 65536, as in
+ * rbgpu_bsi_compare_keys.  Bad arguments are refused on the host, before any launch, with RB_EINVAL.
+ *
+ * The per-slice counts behind Roaring64BitmapSliceIndex.sum (bsi/.../longlong/Roaring64BitmapSliceIndex.java:
+ * 559-570; RoaringBitmapSliceIndex.java:581-592), one andCardinality per slice there, one fused pass per high
+ * key here: counts[i] = |bA[i] AND F| for i < nbits, counts[nbits] = |F|, both restricted to high keys in
+ * [key_lo, key_hi).  F = found, or ebM when found == NULL (as rbgpu_bsi_compare).  counts[nbits] is F's own
+ * cardinality: it is NOT intersected with ebM.  rb_stats: kernel k_bsi_sum, tasks = keys of F walked. */
+int rbgpu_bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                           uint32_t key_hi, uint64_t *counts /* [nbits + 1] */);
+/* Roaring64BitmapSliceIndex.sum (:559-570): *sum = SUM_i counts[i] << i (mod 2^64: Java's long wrap, same bits),
+ * *count = |F| over the whole key range.  The 32-bit class's quirk: RoaringBitmapSliceIndex.sum (:581-592)
+ * weights slice x by (long)(1 << x), an int shift (1 << 31 is negative, and the shift count wraps at 32), so it
+ * agrees with the 64-bit class only for bitCount <= 31.  This call follows Roaring64BitmapSliceIndex (1L << x);
+ * a binding that needs the 32-bit arithmetic applies it to rbgpu_bsi_slice_counts. */
+int rbgpu_bsi_sum(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t *sum, uint64_t *count);
+/* Roaring64BitmapSliceIndex.topK(foundSet, k) (:572-594) -> a one-bitmap set, byte-identical to the
+ * reference's: found == NULL or empty gives an empty bitmap, k >= |found| a clone of found; rows of found
+ * outside ebM act as value 0 (the candidates are never intersected with ebM).  The descent's decisions are
+ * global, so this call takes the whole key range (it cannot be key-range sharded).  BitSliceIndexBase.topK
+ * (buffer/, with its exact-k tie trimming) and transpose are not covered. */
+int rbgpu_bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t k, rbgpu_set **out);
 /* RoaringBitmap.runOptimize (RoaringBitmap.java:2764-2775) of every bitmap of `in` into a new set:
  * each Array / Bitmap container becomes a Run when that is strictly smaller, each Run goes through
  * toEfficientContainer (ArrayContainer.java:1085-1099, BitmapContainer.java:1227-1246,
@@ -496,6 +519,11 @@ int rbgpu_wide_sharded(rbgpu_comm *comm, int sem, const rbgpu_set *in, const uin
 int rbgpu_bsi_compare_sharded(rbgpu_comm *comm, const rbgpu_set *bsi, int op, uint64_t start_or_value, uint64_t end,
                               uint64_t min_value, uint64_t max_value, const rbgpu_set *found, uint32_t key_lo,
                               uint32_t key_hi, rbgpu_set **local, rb_shard_summary *summary);
+/* Roaring64BitmapSliceIndex.sum (:559-570) over a key-range-sharded index: this rank's
+ * rbgpu_bsi_slice_counts over [key_lo, key_hi), then rbgpu_comm_allreduce_sum of the nbits + 1 words, then the
+ * weighted sum (mod 2^64) and |F| of the whole index on every rank.  Collective. */
+int rbgpu_bsi_sum_sharded(rbgpu_comm *comm, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                          uint32_t key_hi, uint64_t *sum, uint64_t *count);
 /* The serialized bytes of the whole result on rank `root`, written to device memory d_dst (cap >=
  * summary->serialized_size; ignored on the other ranks): every rank serializes its shard on its
  * GPU, the shards travel to `root` as one grouped RCCL send/recv, and one kernel there writes the

@@ -156,6 +156,10 @@ SIGNATURES = {
                                     C.POINTER(_P)]),
     "rbgpu_bsi_compare_keys": (C.c_int, [_P, _P, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _P,
                                          C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "rbgpu_bsi_slice_counts": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _U64P]),
+    "rbgpu_bsi_sum": (C.c_int, [_P, _P, _P, _U64P, _U64P]),
+    "rbgpu_bsi_sum_sharded": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _U64P, _U64P]),
+    "rbgpu_bsi_topk": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_P)]),
     "rbgpu_generate_bsi_keys": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.POINTER(_P)]),
     "rbgpu_set_extract": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),

@@ -92,5 +92,28 @@ class Roaring64BitmapSliceIndex:
         return RoaringBitmap(d.ctx.bsi_compare(operation, d, start_or_value, end, self.minValue, self.maxValue,
                                                found))
 
+    # ---- the aggregates (Roaring64BitmapSliceIndex.java:559-594)
+    def sum(self, found_set: Optional[RoaringBitmap]) -> Tuple[int, int]:
+        """sum(foundSet) -> (sum, count): the values of foundSet's rows added up (mod 2^64, the bits of Java's
+        wrapped long) and foundSet's cardinality; None or an empty set gives (0, 0).  One fused pass per high key
+        (rbgpu_bsi_sum).  The 32-bit class weights slice x by (long)(1 << x), an int shift: it agrees for
+        bitCount <= 31, and Context.bsi_slice_counts serves a caller who needs that arithmetic."""
+        if found_set is None or found_set.isEmpty():
+            return 0, 0
+        d = self._device()
+        return d.ctx.bsi_sum(d, found_set._set)
+
+    def topK(self, found_set: Optional[RoaringBitmap], k: int) -> RoaringBitmap:
+        """topK(foundSet, k): the rows of foundSet holding the k largest values, by the reference's descent over the
+        slices (a tie at the k-th value may leave fewer than k rows); None or an empty set gives an empty bitmap,
+        k >= cardinality returns found_set itself (rbgpu_bsi_topk).  BitSliceIndexBase.topK (buffer/, with its
+        exact-k tie trimming) and transpose are not covered."""
+        if found_set is None or found_set.isEmpty():
+            return RoaringBitmap()
+        if k >= found_set.getCardinality():
+            return found_set
+        d = self._device()
+        return RoaringBitmap(d.ctx.bsi_topk(d, found_set._set, k))
+
 
 RoaringBitmapSliceIndex = Roaring64BitmapSliceIndex  # the 32-bit index runs the same compare

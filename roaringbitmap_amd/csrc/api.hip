@@ -1987,6 +1987,52 @@ int rbgpu_bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t sta
   return rbgpu_bsi_compare_keys(ctx, bsi, op, start_or_value, end, min_value, max_value, found, 0, 65536, out);
 }
 
+// the aggregates' arguments: a bsi set of 1..65 bitmaps, found a one-bitmap set of the same context or NULL
+static int check_bsi_agg(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found) {
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!bsi || bsi->ctx != ctx) return fail(RB_EINVAL, "bad bsi set");
+  if (bsi->nb < 1 || bsi->nb > 65) return fail(RB_EINVAL, "a bsi set holds 0..64 slices and the existence bitmap");
+  if (found && (found->ctx != ctx || found->nb != 1)) return fail(RB_EINVAL, "foundSet must be a one-bitmap set");
+  return ensure_h_begin(bsi);
+}
+
+int rbgpu_bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                           uint32_t key_hi, uint64_t *counts) {
+  SETTLE(bsi, found);
+  if (!counts) return fail(RB_EINVAL, "null counts");
+  int rc = check_bsi_agg(ctx, bsi, found);
+  if (rc) return rc;
+  if (key_lo > key_hi || key_hi > 65536) return fail(RB_EINVAL, "bad key range [%u, %u)", key_lo, key_hi);
+  return bsi_slice_counts(ctx, bsi, found, key_lo, key_hi, counts);
+}
+
+// SUM_i counts[i] << i (mod 2^64) and counts[nbits]
+static void bsi_weighted_sum(const uint64_t *counts, uint32_t nbits, uint64_t *sum, uint64_t *count) {
+  uint64_t s = 0;
+  for (uint32_t i = 0; i < nbits; ++i) s += counts[i] << i;
+  *sum = s;
+  *count = counts[nbits];
+}
+
+int rbgpu_bsi_sum(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t *sum, uint64_t *count) {
+  if (!sum || !count) return fail(RB_EINVAL, "null out");
+  uint64_t counts[65] = {};
+  const int rc = rbgpu_bsi_slice_counts(ctx, bsi, found, 0, 65536, counts);
+  if (rc) return rc;
+  bsi_weighted_sum(counts, bsi->nb - 1, sum, count);
+  return RB_OK;
+}
+
+int rbgpu_bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t k, rbgpu_set **out) {
+  SETTLE(bsi, found);
+  if (!out) return fail(RB_EINVAL, "null out");
+  *out = nullptr;
+  const int rc = check_bsi_agg(ctx, bsi, found);
+  if (rc) return rc;
+  return bsi_topk(ctx, bsi, found, k, out);
+}
+
 int rbgpu_set_setup_stats(const rbgpu_set *s, double *ms, uint64_t *bytes) {
   if (!s || !ms || !bytes) return fail(RB_EINVAL, "null argument");
   *ms = s->derive_ms;

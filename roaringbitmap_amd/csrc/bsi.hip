@@ -288,8 +288,11 @@ __global__ __launch_bounds__(256, 2) void k_bsi_chain(SetView bsi, SetView fnd, 
 // closes the kernel.  Each chain keeps its own EQ (registers) and GT / LT accumulator (LDS image)
 // with the same per-step type rules as k_bsi_chain.
 // One chain step (k_bsi_chain's loop body after the slice is staged): TRACK 1 = GT (GE), 2 = LT (LE).
+// ior: the accumulator takes the in-place or (Container.ior), whose types are the static or's except
+// BitmapContainer.ior(ArrayContainer), which keeps a Bitmap even when the result is full (BitmapContainer.java:749-766)
 __device__ __forceinline__ void bsi_step(uint64_t (&e)[kW], Meta &eq, Meta &x, uint32_t *sX, int bit, int track,
-                                         bool spresent, const Meta &sm, const uint32_t *sS, int lane) {
+                                         bool spresent, const Meta &sm, const uint32_t *sS, int lane,
+                                         bool ior = false) {
   if (!eq.present) return; // and/andNot of an absent EQ stay absent; GT/LT unchanged
   const bool feeds = (track == 2 && bit) || (track == 1 && !bit);
   uint64_t t[kW];
@@ -320,6 +323,10 @@ __device__ __forceinline__ void bsi_step(uint64_t (&e)[kW], Meta &eq, Meta &x, u
 #pragma unroll
       for (int j = 0; j < kW; ++j) t[j] |= lds_word(sX, j, lane);
       x = classify(t, lane, eff_or(x0, tm), lr_or(x0, tm), true);
+      if (ior && x0.type == kBitmap && tm.type == kArray) {
+        x.type = kBitmap;
+        x.runs = 0;
+      }
       lds_write_words(sX, t, lane);
     }
     wave_lds_sync();
@@ -658,6 +665,70 @@ static int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *cs, uint32_t nbits
   return RB_OK;
 }
 
+// The tables of a call (ensure_bsi_tables, plus the foundSet's row) and F's keys inside [key_lo, key_hi), F = the
+// foundSet or ebM: ebM's over the whole key range are the set's cached list; a foundSet's or a shard's are
+// listed per call, and their count comes from F's host CSR over the whole range, else by a read-back.
+struct BsiKeys {
+  const uint32_t *d_klist = nullptr;
+  uint32_t nk = 0;
+  uint64_t *d_active = nullptr, *d_pos = nullptr;
+  uint32_t *d_kl = nullptr;
+  void release(rbgpu_ctx *ctx) {
+    for (void *p : {(void *)d_active, (void *)d_pos, (void *)d_kl}) ctx->pool.release(p);
+    d_active = d_pos = nullptr;
+    d_kl = nullptr;
+  }
+};
+static int bsi_keys(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint32_t nbits, const rbgpu_set *found, uint32_t key_lo,
+                    uint32_t key_hi, BsiKeys &ks) {
+  hipStream_t st = ctx->stream;
+  // key -> container tables: rows 0..nbits-1 slices, nbits ebM (the set's, cached), nbits+1 foundSet
+  int rc = ensure_bsi_tables(ctx, bsi, nbits);
+  if (rc) return rc;
+  int32_t *d_table = bsi->bsi_table;
+  if (found) {
+    int32_t *frow = d_table + (uint64_t)(nbits + 1) * 65536;
+    HIPCHK(hipMemsetAsync(frow, 0xFF, 65536 * 4, st));
+    k_bsi_index<<<dim3(64, 1), 256, 0, st>>>(found->view(), 0, frow);
+  }
+  const bool full = key_lo == 0 && key_hi >= 65536;
+  if (!found && (full || !bsi->bsi_nk || (key_lo <= bsi->bsi_kmin && bsi->bsi_kmax < key_hi))) {
+    // every key of ebM lies in the range (the whole range, or a shard holding the index's own keys)
+    ks.d_klist = bsi->bsi_klist;
+    ks.nk = bsi->bsi_nk;
+    return RB_OK;
+  }
+  if (ctx->pool.alloc((void **)&ks.d_active, 65537 * 8ull) || ctx->pool.alloc((void **)&ks.d_pos, 65537 * 8ull) ||
+      ctx->pool.alloc((void **)&ks.d_kl, 65536 * 4ull)) {
+    ks.release(ctx);
+    return fail(RB_ENOMEM, "bsi key list");
+  }
+  const int32_t *frow = d_table + (uint64_t)(found ? nbits + 1 : nbits) * 65536;
+  k_bsi_active<<<256, 256, 0, st>>>(frow, key_lo, key_hi, ks.d_active);
+  const uint64_t *in1[1] = {ks.d_active};
+  uint64_t *out1[1] = {ks.d_pos};
+  scan_blocks_multi(in1, out1, 1, 256, nullptr, st);
+  k_bsi_list<<<256, 256, 0, st>>>(frow, key_lo, key_hi, ks.d_pos, ks.d_kl);
+  ks.d_klist = ks.d_kl;
+  const rbgpu_set *fs = found ? found : bsi;
+  const uint32_t fb = found ? 0u : nbits;
+  hipError_t e = hipSuccess;
+  if (full && !ensure_h_begin(fs)) {
+    ks.nk = (uint32_t)(fs->h_begin[fb + 1] - fs->h_begin[fb]);
+    e = hipGetLastError();
+  } else {
+    e = hipMemcpyAsync(ctx->h_pinned, ks.d_pos + 256, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    ks.nk = (uint32_t)ctx->h_pinned[0];
+  }
+  if (e != hipSuccess) {
+    ks.release(ctx);
+    return fail(RB_EDEVICE, "bsi key list failed: %s", hipGetErrorString(e));
+  }
+  return RB_OK;
+}
+
 // RANGE over nk >= 1 keys of F: k_bsi_range writes the result set (CSR, SoA, payload slots) and the call's
 // counters itself; the host returns on the call's sequence number (wait_call_seq).
 static int bsi_range_one_launch(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, const int32_t *d_table,
@@ -701,6 +772,26 @@ static int bsi_range_one_launch(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgp
   return RB_OK;
 }
 
+// An empty one-bitmap result (new RoaringBitmap()); rb_stats describes it: no kernel ran, nothing counted.
+static int empty_result(rbgpu_ctx *ctx, rbgpu_set **out) {
+  rbgpu_set *e = new rbgpu_set;
+  const int rc = set_alloc(ctx, e, 1, 0, 16);
+  if (rc) {
+    delete e;
+    return rc;
+  }
+  const uint64_t hb[2] = {0, 0};
+  if (hipMemcpyAsync(e->begin, hb, 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+    rbgpu_set_free(e);
+    return fail(RB_EDEVICE, "empty result");
+  }
+  e->h_begin = {0, 0};
+  for (int i = 0; i < kStatWords; ++i) ctx->words[i] = 0;
+  *out = e;
+  return stats_fill(ctx, 0, 0, nullptr, 0, false);
+}
+
 int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, uint64_t end, uint64_t vmin,
                 uint64_t vmax, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out) {
   const uint32_t nbits = bsi->nb - 1;
@@ -724,21 +815,7 @@ int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, ui
       ctx->words[7] = card;
       return stats_fill(ctx, 0, r->nc, nullptr, 0, false);
     };
-    if (sc == 0) {
-      rbgpu_set *e = new rbgpu_set;
-      const int rc = set_alloc(ctx, e, 1, 0, 16);
-      if (rc) {
-        delete e;
-        return rc;
-      }
-      const uint64_t hb[2] = {0, 0};
-      HIPCHK(hipMemcpyAsync(e->begin, hb, 16, hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
-      LAUNCHCHK();
-      e->h_begin = {0, 0};
-      *out = e;
-      return shortcut_stats(e, 0);
-    }
+    if (sc == 0) return empty_result(ctx, out);
     if (!found) {
       int rc = rbgpu_set_extract(bsi, nbits, 1, out);
       uint64_t card = 0;
@@ -753,54 +830,14 @@ int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, ui
     const uint32_t ai = nbits, bi = 0;
     return rbgpu_pairwise(ctx, RB_AND, bsi, found, &ai, &bi, 1, out); // its own stats: the AND's answer
   }
-  // key -> container tables: rows 0..nbits-1 slices, nbits ebM (the set's, cached), nbits+1 foundSet
-  int rc = ensure_bsi_tables(ctx, bsi, nbits);
+  // key -> container tables and F's keys in the range
+  BsiKeys ks;
+  int rc = bsi_keys(ctx, bsi, nbits, found, key_lo, key_hi, ks);
   if (rc) return rc;
-  int32_t *d_table = bsi->bsi_table;
-  if (found) {
-    int32_t *frow = d_table + (uint64_t)(nbits + 1) * 65536;
-    HIPCHK(hipMemsetAsync(frow, 0xFF, 65536 * 4, st));
-    k_bsi_index<<<dim3(64, 1), 256, 0, st>>>(found->view(), 0, frow);
-  }
-  // F's keys: ebM's over the whole key range are the set's cached list; a foundSet's or a shard's are
-  // listed per call, and their count comes from F's host CSR over the whole range, else by a read-back
-  uint32_t nk = 0;
-  const uint32_t *d_klist = nullptr;
-  uint64_t *d_active = nullptr, *d_pos = nullptr;
-  uint32_t *d_kl = nullptr;
-  auto release = [&]() {
-    for (void *p : {(void *)d_active, (void *)d_pos, (void *)d_kl}) ctx->pool.release(p);
-  };
-  const bool full = key_lo == 0 && key_hi >= 65536;
-  if (!found && (full || !bsi->bsi_nk || (key_lo <= bsi->bsi_kmin && bsi->bsi_kmax < key_hi))) {
-    // every key of ebM lies in the range (the whole range, or a shard holding the index's own keys)
-    d_klist = bsi->bsi_klist;
-    nk = bsi->bsi_nk;
-  } else {
-    if (ctx->pool.alloc((void **)&d_active, 65537 * 8ull) || ctx->pool.alloc((void **)&d_pos, 65537 * 8ull) ||
-        ctx->pool.alloc((void **)&d_kl, 65536 * 4ull)) {
-      release();
-      return fail(RB_ENOMEM, "bsi key list");
-    }
-    const int32_t *frow = d_table + (uint64_t)(found ? nbits + 1 : nbits) * 65536;
-    k_bsi_active<<<256, 256, 0, st>>>(frow, key_lo, key_hi, d_active);
-    const uint64_t *in1[1] = {d_active};
-    uint64_t *out1[1] = {d_pos};
-    scan_blocks_multi(in1, out1, 1, 256, nullptr, st);
-    k_bsi_list<<<256, 256, 0, st>>>(frow, key_lo, key_hi, d_pos, d_kl);
-    d_klist = d_kl;
-    const rbgpu_set *fs = found ? found : bsi;
-    const uint32_t fb = found ? 0u : nbits;
-    if (full && !ensure_h_begin(fs)) {
-      nk = (uint32_t)(fs->h_begin[fb + 1] - fs->h_begin[fb]);
-      LAUNCHCHK();
-    } else {
-      HIPCHK(hipMemcpyAsync(ctx->h_pinned, d_pos + 256, 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      LAUNCHCHK();
-      nk = (uint32_t)ctx->h_pinned[0];
-    }
-  }
+  const int32_t *d_table = bsi->bsi_table;
+  const uint32_t *d_klist = ks.d_klist;
+  const uint32_t nk = ks.nk;
+  auto release = [&]() { ks.release(ctx); };
   // result set: one 8 KiB slot per key of F, compacted at the end
   rbgpu_set *res = new rbgpu_set;
   rc = set_alloc(ctx, res, 1, nk, (uint64_t)std::max<uint32_t>(nk, 1) * kBitmapBytes);
@@ -840,6 +877,376 @@ int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, ui
   }
   *out = res;
   return RB_OK;
+}
+
+// ---------------------------------------------------------------- aggregates: sum and topK
+// Roaring64BitmapSliceIndex.sum / topK (bsi/.../longlong/Roaring64BitmapSliceIndex.java:559-594).  Both walk
+// the slices of one high key with the found set's container held as a register bitmap, as k_bsi_chain holds EQ.
+
+// The slices' containers at one key, lane i <-> slice i (nbits <= 64), and the staged walk over them
+// (k_bsi_chain's loop head: payloads of at most 8 KiB arrive through registers, a Run of more than 2047 runs is
+// toggled straight from global).
+struct SliceDesc {
+  int32_t sc;
+  int st;
+  uint32_t scard, sruns;
+  uint64_t soff;
+  __device__ __forceinline__ void load(const SetView &bsi, const int32_t *table, uint32_t nbits, uint32_t key, int lane) {
+    sc = lane < (int)nbits ? table[(uint64_t)lane * 65536 + key] : -1;
+    st = 0;
+    scard = sruns = 0;
+    soff = 0;
+    if (sc >= 0) {
+      st = bsi.type[sc];
+      scard = bsi.card[sc];
+      sruns = bsi.nruns[sc];
+      soff = bsi.off[sc];
+    }
+  }
+  __device__ __forceinline__ bool present(int i) const { return (int)readlane((uint32_t)sc, i) >= 0; }
+  __device__ __forceinline__ Meta meta(int i) const {
+    return Meta{1, (int)readlane((uint32_t)st, i), (int)readlane(scard, i), (int)readlane(sruns, i)};
+  }
+  __device__ __forceinline__ uint32_t bytes(int i) const {
+    return (uint32_t)payload_bytes((int)readlane((uint32_t)st, i), readlane(scard, i), readlane(sruns, i));
+  }
+  __device__ __forceinline__ const uint8_t *ptr(const SetView &bsi, int i) const {
+    return bsi.payload + pack2(readlane((uint32_t)soff, i), readlane((uint32_t)(soff >> 32), i));
+  }
+  // slice i's payload into pq (i < 0, an absent slice or a payload past 8 KiB: one dummy chunk)
+  __device__ __forceinline__ void prefetch(uint4 (&pq)[8], const SetView &bsi, int i, int lane) const {
+    const bool ok = i >= 0 && present(i) && bytes(i) <= (uint32_t)kBitmapBytes;
+    load_chunks(pq, ok ? ptr(bsi, i) : bsi.payload, ok ? bytes(i) : 16u, lane);
+  }
+  // present slice i (metadata sm, payload prefetched in pq) -> membership image sS
+  __device__ __forceinline__ void stage(const uint4 (&pq)[8], const SetView &bsi, int i, const Meta &sm, uint32_t *sS,
+                                        int lane) const {
+    if (payload_bytes(sm.type, sm.card, sm.runs) > (uint64_t)kBitmapBytes) {
+      lds_zero(sS, lane);
+      wave_lds_sync();
+      const uint32_t *r32 = reinterpret_cast<const uint32_t *>(ptr(bsi, i));
+      for (int k = lane; k < sm.runs; k += 64) toggle_run(sS, r32[k]);
+      wave_lds_sync();
+      toggles_to_words_lds(sS, lane);
+      wave_lds_sync();
+    } else {
+      stage_from_chunks(sm.type, pq, (uint32_t)sm.card, (uint32_t)sm.runs, sS, lane);
+    }
+  }
+};
+
+// sum's slice counts: one wave per key of F.  F's container is a register bitmap, every slice that has a container
+// at the key is staged once (the next one's payload in flight) and popcount(F & S) is reduced over the wave so that
+// lane i keeps slice i's count; an absent slice costs nothing.  The block's four waves add up in LDS and leave as
+// one 64-lane u64 add into the block's stripe of acc[kStripes][kAccRow] (word 64: |F|); k_bsi_sum_fold sums the
+// stripes.  Integer adds commute: the counts are exact whatever the order.
+constexpr int kAccRow = 65;
+__global__ __launch_bounds__(256, 2) void k_bsi_sum(SetView bsi, SetView fnd, int has_found,
+                                                    const int32_t *__restrict__ table, uint32_t nbits,
+                                                    const uint32_t *__restrict__ klist, uint32_t nk,
+                                                    uint64_t *__restrict__ acc, uint64_t *stats) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[4][2048];
+  __shared__ uint32_t part[4][kAccRow];
+  __shared__ uint64_t red[4];
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t q = xcd_swizzle(blockIdx.x, gridDim.x) * 4 + wv;
+  uint32_t mine = 0, fcard = 0;
+  uint64_t inb = 0;
+  if (q < nk) { // wave-uniform
+    uint32_t *sS = lds[wv];
+    const uint32_t key = klist[q];
+    uint64_t e[kW];
+    const Meta fm = stage_global(has_found ? fnd : bsi, table[(uint64_t)(has_found ? nbits + 1 : nbits) * 65536 + key],
+                                 sS, lane); // present: the keys come from F
+    lds_read_words(sS, e, lane);
+    wave_lds_sync();
+    fcard = (uint32_t)fm.card;
+    inb += payload_bytes(fm.type, fm.card, fm.runs) + 16;
+    SliceDesc d;
+    d.load(bsi, table, nbits, key, lane);
+    uint64_t todo = __ballot(d.sc >= 0);
+    uint4 pq[8];
+    if (todo) d.prefetch(pq, bsi, __builtin_ctzll(todo), lane);
+    while (todo) {
+      const int i = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const Meta sm = d.meta(i);
+      inb += payload_bytes(sm.type, sm.card, sm.runs) + 16;
+      d.stage(pq, bsi, i, sm, sS, lane);
+      // ---- the next present slice in flight during this one's count
+      __builtin_amdgcn_sched_barrier(0);
+      if (todo) d.prefetch(pq, bsi, __builtin_ctzll(todo), lane);
+      uint32_t p = 0;
+#pragma unroll
+      for (int j = 0; j < kW; ++j) p += (uint32_t)__popcll(e[j] & lds_word(sS, j, lane));
+      wave_lds_sync();
+      const uint32_t tot = wave_sum_u32(p);
+      if (lane == i) mine = tot;
+    }
+  }
+  part[wv][lane] = mine;
+  if (lane == 0) {
+    part[wv][64] = fcard;
+    red[wv] = inb;
+  }
+  __syncthreads();
+  if (wv != 0) return;
+  const uint32_t stripe = blockIdx.x & (kStripes - 1);
+  const uint64_t c = (uint64_t)part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+  if (c) atomicAdd((unsigned long long *)&acc[stripe * kAccRow + lane], (unsigned long long)c);
+  if (lane == 0) {
+    const uint64_t f = (uint64_t)part[0][64] + part[1][64] + part[2][64] + part[3][64];
+    if (f) atomicAdd((unsigned long long *)&acc[stripe * kAccRow + 64], (unsigned long long)f);
+    const uint64_t b = red[0] + red[1] + red[2] + red[3];
+    if (b) atomicAdd((unsigned long long *)&stats[0 * kStripes + stripe], (unsigned long long)b);
+  }
+}
+// out[i] = the stripes' sum of word i (slice i's count), out[nbits] = |F| (word 64 of the rows)
+__global__ __launch_bounds__(128) void k_bsi_sum_fold(const uint64_t *__restrict__ acc, uint32_t nbits,
+                                                      uint64_t *__restrict__ out) {
+  const uint32_t t = threadIdx.x;
+  if (t > nbits) return;
+  const uint32_t w = t == nbits ? 64u : t;
+  uint64_t s = 0;
+  for (int k = 0; k < kStripes; ++k) s += acc[k * kAccRow + w];
+  out[t] = s;
+}
+
+int bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
+                     uint64_t *counts) {
+  const uint32_t nbits = bsi->nb - 1;
+  hipStream_t st = ctx->stream;
+  stats_begin(ctx);
+  BsiKeys ks;
+  int rc = bsi_keys(ctx, bsi, nbits, found, key_lo, key_hi, ks);
+  if (rc) return rc;
+  uint64_t *acc = nullptr; // [kStripes][kAccRow], then the folded nbits + 1 words
+  if (ctx->pool.alloc((void **)&acc, (kStripes + 1ull) * kAccRow * 8)) {
+    ks.release(ctx);
+    return fail(RB_ENOMEM, "bsi slice counts");
+  }
+  uint64_t *folded = acc + kStripes * kAccRow;
+  hipError_t e = hipMemsetAsync(acc, 0, (kStripes + 1ull) * kAccRow * 8, st);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
+  if (e == hipSuccess && ks.nk) {
+    k_bsi_sum<<<nblk(ks.nk, 4), 256, 0, st>>>(bsi->view(), found ? found->view() : bsi->view(), found != nullptr,
+                                              bsi->bsi_table, nbits, ks.d_klist, ks.nk, acc, ctx->d_stats);
+    k_bsi_sum_fold<<<1, 128, 0, st>>>(acc, nbits, folded);
+  }
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], st);
+  // the call's one read-back (stats_end waits for the stream)
+  if (e == hipSuccess) e = hipMemcpyAsync(counts, folded, (nbits + 1ull) * 8, hipMemcpyDeviceToHost, st);
+  ctx->pool.release(acc); // stream-ordered: handed out again only to later work on this stream
+  const uint32_t nk = ks.nk;
+  ks.release(ctx);
+  if (e != hipSuccess) return fail(RB_EDEVICE, "bsi slice counts failed: %s", hipGetErrorString(e));
+  const KernelSpan spans[1] = {{"k_bsi_sum", 0, -1, nk}};
+  return stats_end(ctx, nk, 0, spans, 1);
+}
+
+// ---- topK.  The decision at slice x (keep the rows with the bit, or emit them and go on with the rest) needs the
+// global count |cand AND bA[x]|, so the keys are not independent: phase A carries the dependence in stream order,
+// one launch per slice, and leaves the counts; phase B, with every decision known, is key-local again.
+//
+// Phase A, the launch of slice x, one wave per key of found.  The candidates of a key are a dense 8 KiB image in
+// global memory.  A wave first replays the chain of decisions of the slices above x from counts[] (final: their
+// launches ended before this one began) and from k and |found|, which every wave does alike, so no wave waits for
+// another; once the chain is over (k used up, or no candidate left) the launch returns at once.  It then applies
+// slice x+1's decision to its image (and / andNot with bA[x+1]) and adds |cand AND bA[x]| to counts[x].  A slice
+// container is read twice over the phase: counted in its own launch, applied in the next.
+__global__ __launch_bounds__(256, 2) void k_bsi_topk_count(SetView bsi, SetView fnd, const int32_t *__restrict__ table,
+                                                           uint32_t nbits, int x, uint64_t k0, uint64_t card0,
+                                                           const uint32_t *__restrict__ klist, uint32_t nk,
+                                                           uint8_t *__restrict__ img, uint64_t *counts) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[4][2048];
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t q = xcd_swizzle(blockIdx.x, gridDim.x) * 4 + wv;
+  if (q >= nk) return;
+  const uint64_t cv = lane < (int)nbits && lane > x ? counts[lane] : 0ull;
+  uint64_t k = k0, cand = card0;
+  int keep = 0; // slice x+1's decision: 1 = cand.and(bA[x+1]), 0 = re.or(...), cand.andNot(bA[x+1])
+  for (int y = (int)nbits - 1; y > x; --y) {
+    if (!cand || !k) return;
+    const uint64_t c = pack2(readlane((uint32_t)cv, y), readlane((uint32_t)(cv >> 32), y));
+    keep = c > k;
+    if (keep) {
+      cand = c;
+    } else {
+      cand -= c;
+      k -= c;
+    }
+  }
+  if (!cand || !k) return;
+  uint32_t *sS = lds[wv];
+  const uint32_t key = klist[q];
+  uint8_t *im = img + (uint64_t)q * kBitmapBytes;
+  uint64_t e[kW];
+  if (x == (int)nbits - 1) { // candidates = foundSet.clone()
+    stage_global(fnd, table[(uint64_t)(nbits + 1) * 65536 + key], sS, lane);
+    lds_read_words(sS, e, lane);
+    wave_lds_sync();
+  } else {
+    load_bitmap(im, e, lane);
+    const Meta sm = stage_global(bsi, table[(uint64_t)(x + 1) * 65536 + key], sS, lane);
+#pragma unroll
+    for (int j = 0; j < kW; ++j) {
+      const uint64_t sw = sm.present ? lds_word(sS, j, lane) : 0ull;
+      e[j] = keep ? (e[j] & sw) : (e[j] & ~sw);
+    }
+    wave_lds_sync();
+  }
+  {
+    uint4 *o = reinterpret_cast<uint4 *>(im);
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      o[j * 64 + lane] = make_uint4((uint32_t)e[2 * j], (uint32_t)(e[2 * j] >> 32), (uint32_t)e[2 * j + 1],
+                                    (uint32_t)(e[2 * j + 1] >> 32));
+  }
+  const Meta sm = stage_global(bsi, table[(uint64_t)x * 65536 + key], sS, lane);
+  if (!sm.present) return;
+  uint32_t p = 0;
+#pragma unroll
+  for (int j = 0; j < kW; ++j) p += (uint32_t)__popcll(e[j] & lds_word(sS, j, lane));
+  const uint32_t tot = wave_sum_u32(p);
+  if (lane == 0 && tot) atomicAdd((unsigned long long *)&counts[x], (unsigned long long)tot);
+}
+
+// Phase B, the typed emit: k_bsi_chain's GT-tracking loop (bsi_step, track 1) with EQ = found's container, the
+// decisions as the predicate (bit x set: cand.and(bA[x]); clear: re.or(and(cand, bA[x])), cand.andNot(bA[x])), the
+// loop ending at the descent's last slice `stop`, the accumulator taking Roaring64Bitmap's in-place or, and no
+// final AND: the result is the accumulator.
+__global__ __launch_bounds__(256, 2) void k_bsi_topk_emit(SetView bsi, SetView fnd, const int32_t *__restrict__ table,
+                                                          uint32_t nbits, uint64_t pred, int stop,
+                                                          const uint32_t *__restrict__ klist, uint32_t nk,
+                                                          uint8_t *__restrict__ out, WideOut wo, uint64_t *stats) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[4][2][2048];
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t q = xcd_swizzle(blockIdx.x, gridDim.x) * 4 + wv;
+  if (q >= nk) return;
+  uint32_t *sS = lds[wv][0], *sX = lds[wv][1];
+  const uint32_t key = klist[q];
+  uint64_t e[kW];
+  Meta eq = stage_global(fnd, table[(uint64_t)(nbits + 1) * 65536 + key], sS, lane); // present: found's own key
+  lds_read_words(sS, e, lane);
+  wave_lds_sync();
+  uint64_t inb = payload_bytes(eq.type, eq.card, eq.runs) + 16;
+  Meta x{0, 0, 0, 0};
+  SliceDesc d;
+  d.load(bsi, table, nbits, key, lane);
+  uint4 pq[8];
+  d.prefetch(pq, bsi, (int)nbits - 1, lane);
+  for (int i = (int)nbits - 1; i >= stop; --i) {
+    const bool spresent = d.present(i);
+    Meta sm{0, 0, 0, 0};
+    if (spresent) {
+      sm = d.meta(i);
+      inb += payload_bytes(sm.type, sm.card, sm.runs) + 16;
+      d.stage(pq, bsi, i, sm, sS, lane);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (i > stop) d.prefetch(pq, bsi, i - 1, lane);
+    bsi_step(e, eq, x, sX, (int)((pred >> i) & 1), 1, spresent, sm, sS, lane, true);
+  }
+  uint64_t t[kW];
+#pragma unroll
+  for (int j = 0; j < kW; ++j) t[j] = x.present ? lds_word(sX, j, lane) : 0ull;
+  wave_lds_sync();
+  const int ty = x.present ? x.type : kEmpty;
+  if (x.present) emit_container(ty, t, x.card, x.runs, out + (uint64_t)q * kBitmapBytes, sS, lane);
+  if (lane == 0) {
+    wo.type[q] = (uint8_t)ty;
+    wo.card[q] = (uint32_t)(x.present ? x.card : 0);
+    wo.nruns[q] = (uint16_t)(ty == kRun ? x.runs : 0);
+    atomicAdd((unsigned long long *)&stats[0 * kStripes + (q & (kStripes - 1))], (unsigned long long)inb);
+    if (x.present)
+      atomicAdd((unsigned long long *)&stats[1 * kStripes + (q & (kStripes - 1))],
+                (unsigned long long)(payload_bytes(ty, x.card, x.runs) + (ty == kRun ? 2 : 0) + 16));
+  }
+}
+
+int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t k, rbgpu_set **out) {
+  const uint32_t nbits = bsi->nb - 1;
+  hipStream_t st = ctx->stream;
+  uint64_t fcard = 0;
+  if (found) {
+    const int rc = rbgpu_set_cardinalities(found, &fcard);
+    if (rc) return rc;
+  }
+  stats_begin(ctx);
+  if (!fcard) return empty_result(ctx, out);                       // null or empty foundSet: new Roaring64Bitmap()
+  if (k >= fcard) return rbgpu_set_extract(found, 0, 1, out);      // foundSet itself: here a clone, the same bytes
+  if (!k || !nbits) return empty_result(ctx, out);                 // the loop does not run: re stays empty
+  BsiKeys ks;
+  int rc = bsi_keys(ctx, bsi, nbits, found, 0, 65536, ks);
+  if (rc) return rc;
+  const uint32_t nk = ks.nk; // >= 1: found is not empty
+  const SetView bv = bsi->view(), fv = found->view();
+  uint8_t *img = nullptr;
+  uint64_t *counts = nullptr;
+  rbgpu_set *res = nullptr;
+  KeyedSlots fin;
+  bool slots = false;
+  auto done = [&](int r) {
+    ctx->pool.release(img);
+    ctx->pool.release(counts);
+    if (slots) fin.release(ctx, false);
+    ks.release(ctx);
+    if (r && res) rbgpu_set_free(res);
+    return r;
+  };
+  if (ctx->pool.alloc((void **)&img, (uint64_t)nk * kBitmapBytes) || ctx->pool.alloc((void **)&counts, 64 * 8))
+    return done(fail(RB_ENOMEM, "bsi topK candidates of %u keys", nk));
+  // ---- phase A: one launch per slice, no host wait in between; one read-back of the counts
+  hipError_t e = hipMemsetAsync(counts, 0, 64 * 8, st);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
+  if (e == hipSuccess)
+    for (int x = (int)nbits - 1; x >= 0; --x)
+      k_bsi_topk_count<<<nblk(nk, 4), 256, 0, st>>>(bv, fv, bsi->bsi_table, nbits, x, k, fcard, ks.d_klist, nk, img, counts);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], st);
+  uint64_t hc[64];
+  if (e == hipSuccess) e = hipMemcpyAsync(hc, counts, 64 * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi topK descent failed: %s", hipGetErrorString(e)));
+  // the decisions, as the kernels replayed them (Roaring64BitmapSliceIndex.java:582-592)
+  uint64_t pred = 0, kk = k, cand = fcard;
+  int stop = (int)nbits;
+  for (int x = (int)nbits - 1; x >= 0 && cand && kk; --x) {
+    stop = x;
+    if (hc[x] > kk) {
+      pred |= 1ull << x;
+      cand = hc[x];
+    } else {
+      cand -= hc[x];
+      kk -= hc[x];
+    }
+  }
+  // ---- phase B: every key on its own again
+  res = new rbgpu_set;
+  rc = set_alloc(ctx, res, 1, nk, (uint64_t)nk * kBitmapBytes);
+  if (rc) {
+    delete res;
+    res = nullptr;
+    return done(rc);
+  }
+  rc = fin.alloc(ctx, nk, false);
+  slots = true;
+  if (rc) return done(rc);
+  if (hipEventRecord(ctx->ev[3], st) != hipSuccess) return done(fail(RB_EDEVICE, "event record failed"));
+  k_bsi_topk_emit<<<nblk(nk, 4), 256, 0, st>>>(bv, fv, bsi->bsi_table, nbits, pred, stop, ks.d_klist, nk, res->payload,
+                                               fin.wo, ctx->d_stats);
+  if (hipEventRecord(ctx->ev[4], st) != hipSuccess) return done(fail(RB_EDEVICE, "event record failed"));
+  rc = compact_keyed(ctx, ks.d_klist, nk, fin.wo, res);
+  const KernelSpan spans[2] = {{"k_bsi_topk_count", -1, -1, (uint64_t)nk * nbits},
+                               {"k_bsi_topk_emit", 0, 1, nk, ctx->ev[3], ctx->ev[4]}};
+  if (!rc) rc = stats_end(ctx, nk, 0, spans, 2);
+  if (rc) return done(rc);
+  keyed_result_count(ctx, res);
+  *out = res;
+  return done(RB_OK);
 }
 
 // this file's code object, loaded at context creation (warm_code_objects, api.hip)

@@ -792,6 +792,26 @@ int rbgpu_bsi_compare_sharded(rbgpu_comm *c, const rbgpu_set *bsi, int op, uint6
   return rc;
 }
 
+int rbgpu_bsi_sum_sharded(rbgpu_comm *c, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                          uint32_t key_hi, uint64_t *sum, uint64_t *count) {
+  if (!c || !sum || !count) return fail(RB_EINVAL, "null argument");
+  uint64_t counts[65] = {};
+  int rc = need_device(c);
+  if (!rc) rc = rbgpu_bsi_slice_counts(c->ctx, bsi, found, key_lo, key_hi, counts);
+  if (rc) std::fill(counts, counts + 65, 0ull);
+  // every rank joins the exchange of the nbits + 1 words, failed or not (the ranks hold the same index shape)
+  const uint32_t nb = bsi && bsi->nb >= 1 && bsi->nb <= 65 ? bsi->nb : 1;
+  const int rx = rbgpu_comm_allreduce_sum(c, counts, nb);
+  if (rc) return rc;
+  if (rx) return rx;
+  const uint32_t nbits = nb - 1;
+  uint64_t s = 0;
+  for (uint32_t i = 0; i < nbits; ++i) s += counts[i] << i;
+  *sum = s;
+  *count = counts[nbits];
+  return RB_OK;
+}
+
 int rbgpu_shard_gather_serialized(rbgpu_comm *c, const rbgpu_set *local, const rb_shard_summary *summary, int root,
                                   uint8_t *d_dst, uint64_t cap) {
   SETTLE(local);

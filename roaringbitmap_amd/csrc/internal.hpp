@@ -327,6 +327,11 @@ uint64_t keyed_result_count(rbgpu_ctx *ctx, rbgpu_set *res);
 // [key_lo, key_hi) are computed (a key-range shard of the answer)
 int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, uint64_t end, uint64_t vmin,
                 uint64_t vmax, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
+// bsi.hip, the aggregates: counts[i] = |bA[i] AND F| (i < nbits) and counts[nbits] = |F| over the high keys in
+// [key_lo, key_hi), F = found or ebM; Roaring64BitmapSliceIndex.topK(found, k) as a new one-bitmap set
+int bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
+                     uint64_t *counts);
+int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t k, rbgpu_set **out);
 // api.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
 int set_key_subset(const rbgpu_set *s, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
 int set_gather(const rbgpu_set *s, const uint32_t *idx, uint32_t n, rbgpu_set **out);

@@ -567,6 +567,35 @@ class Context:
                                                C.byref(out)))
         return DeviceSet(self, out.value)
 
+    def bsi_slice_counts(self, bsi: DeviceSet, found: Optional[DeviceSet] = None, key_range=None) -> np.ndarray:
+        """counts[i] = |bA[i] AND F| for every slice and counts[nbits] = |F| (F = found, or ebM) over the high keys
+        of key_range (default: all), in one fused pass per key (rbgpu_bsi_slice_counts)."""
+        lo, hi = key_range if key_range is not None else (0, 65536)
+        out = np.zeros(len(bsi), np.uint64)
+        L.check(L.lib().rbgpu_bsi_slice_counts(self.h, bsi.h, found.h if found is not None else None, int(lo), int(hi),
+                                               out.ctypes.data_as(L._U64P)))
+        return out
+
+    def bsi_sum(self, bsi: DeviceSet, found: Optional[DeviceSet] = None) -> Tuple[int, int]:
+        """Roaring64BitmapSliceIndex.sum over a device BSI: (sum mod 2^64, |F|) (rbgpu_bsi_sum)."""
+        s, c = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().rbgpu_bsi_sum(self.h, bsi.h, found.h if found is not None else None, C.byref(s), C.byref(c)))
+        return int(s.value), int(c.value)
+
+    def bsi_sum_sharded(self, comm: "Comm", bsi: DeviceSet, key_range, found: Optional[DeviceSet] = None):
+        """This rank's key range of the sum, all-reduced over comm's ranks (Comm.bsi_sum_sharded)."""
+        return comm.bsi_sum_sharded(bsi, key_range, found)
+
+    def bsi_topk(self, bsi: DeviceSet, found: Optional[DeviceSet], k: int) -> DeviceSet:
+        """Roaring64BitmapSliceIndex.topK(foundSet, k) as a one-bitmap set (rbgpu_bsi_topk); whole key range
+        only: the descent's decisions are global."""
+        if k < 0:
+            raise ValueError("k must be non-negative")
+        out = C.c_void_p()
+        L.check(L.lib().rbgpu_bsi_topk(self.h, bsi.h, found.h if found is not None else None, min(int(k), 2**64 - 1),
+                                       C.byref(out)))
+        return DeviceSet(self, out.value)
+
     def generate_bsi(self, nslices: int, nrows: int, seed: int = 42, key_range=None) -> DeviceSet:
         """The synthetic BSI of SURVEY §8d config 5, or its [lo, hi) key-range shard."""
         a = C.c_void_p()
@@ -643,6 +672,14 @@ class Comm:
                                                   found.h if found is not None else None, int(key_range[0]),
                                                   int(key_range[1]), C.byref(out), C.byref(summ)))
         return DeviceSet(self.ctx, out.value), _summary(summ)
+
+    def bsi_sum_sharded(self, bsi: DeviceSet, key_range, found: Optional[DeviceSet] = None) -> Tuple[int, int]:
+        """(sum mod 2^64, |F|) of the whole index on every rank: this rank's slice counts over key_range, then one
+        all-reduce of nbits + 1 words (rbgpu_bsi_sum_sharded)."""
+        s, c = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().rbgpu_bsi_sum_sharded(self.h, bsi.h, found.h if found is not None else None,
+                                              int(key_range[0]), int(key_range[1]), C.byref(s), C.byref(c)))
+        return int(s.value), int(c.value)
 
     def gather_serialized(self, local: DeviceSet, summary: dict, root: int = 0) -> Optional[bytes]:
         """The whole result's RoaringFormatSpec bytes on `root` (None elsewhere), assembled on the

@@ -260,6 +260,32 @@ class ShardedBsi(ShardedWide):
         local = ctx.bsi_compare(op, bsi, start, end, min_value, max_value, found, key_range=key_range)
         return self.finish(local, key_range, local.summaries()[0])
 
+    def sum(self, ctx, bsi, key_range: Tuple[int, int], found=None, local_counts=None) -> Tuple[int, int]:
+        """Roaring64BitmapSliceIndex.sum(foundSet) of the whole index, on every rank: (sum mod 2^64, |F|).
+
+        The per-slice counts |bA[i] AND F| and |F| are sums over the high keys, so rank r computes them over its
+        key range (Context.bsi_slice_counts, or `local_counts`, the nbits + 1 words a caller computed some other
+        way: the CPU tests pass the oracle's) and one all_reduce of nbits + 1 int64 (the bits of the unsigned
+        words) adds the ranks up; the weights 1 << i are applied after it.  topK is not sharded: the decisions of
+        its descent are global."""
+        import torch
+        if local_counts is None:
+            local_counts = ctx.bsi_slice_counts(bsi, found, key_range)
+        c = np.ascontiguousarray(np.asarray(local_counts, dtype=np.uint64))
+        t = torch.from_numpy(c.view(np.int64).copy())
+        if self.device is not None:
+            t = t.to(self.device)
+        self.dist.all_reduce(t)
+        tot = t.cpu().numpy().view(np.uint64)
+        return weighted_sum(tot)
+
+
+def weighted_sum(counts) -> Tuple[int, int]:
+    """(SUM_i counts[i] << i mod 2^64, counts[nbits]) of nbits + 1 slice counts (Roaring64BitmapSliceIndex.sum)."""
+    nbits = len(counts) - 1
+    s = sum(int(counts[i]) << i for i in range(nbits)) & (2**64 - 1)
+    return s, int(counts[nbits])
+
 
 @dataclass
 class PairShardResult:
