@@ -328,8 +328,33 @@ int rbgpu_bsi_sum(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, 
  * reference's: found == NULL or empty gives an empty bitmap, k >= |found| a clone of found; rows of found
  * outside ebM act as value 0 (the candidates are never intersected with ebM).  The descent's decisions are
  * global, so this call takes the whole key range (it cannot be key-range sharded).  BitSliceIndexBase.topK
- * (buffer/, with its exact-k tie trimming) and transpose are not covered. */
+ * (buffer/, with its exact-k tie trimming) is not covered; the rows' values come from rbgpu_bsi_get_values. */
 int rbgpu_bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t k, rbgpu_set **out);
+/* The value read-back of a BSI, on the device.  `bsi`, `found` and the key range as for rbgpu_bsi_slice_counts
+ * (nbits = 0 is legal: every value is 0); bad arguments give RB_EINVAL before any launch.  Values are the true
+ * unsigned 64-bit values: bit i of a row's value is its membership in bA[i].  The reference's valueAt
+ * (Roaring64BitmapSliceIndex.java:128-131, RoaringBitmapSliceIndex.java:181) accumulates `1 << i` in an int, so
+ * the two agree for bitCount <= 31 (the convention of rbgpu_bsi_sum).
+ *
+ * BitSliceIndexBase.toPairList(foundSet) (bsi/.../buffer/BitSliceIndexBase.java:534-549; transpose,
+ * Roaring64BitmapSliceIndex.java:596-601, is a loop over the same values): the (columnId, value) pairs of the rows
+ * of ebM AND found (found NULL: ebM), ascending columnId, high keys [key_lo, key_hi).  A row of ebM whose value is
+ * 0 is exported as (col, 0); a row of found outside ebM is not exported.  *count = number of pairs.
+ * cols == NULL && vals == NULL: count only.  count > cap: RB_EINVAL, *count still set, nothing written.
+ * rb_stats: main kernel k_bsi_values, tasks = keys of F walked, output_bytes = 12 * count, result_cardinality =
+ * count, input_bytes = payload + 16 B of F's and ebM's containers at those keys and of the slices' containers at
+ * the keys that export a row. */
+int rbgpu_bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
+                     uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count);
+/* The same into device memory (cap entries each); count on the host; synchronous like rbgpu_set_serialize_device.
+ * The count and the gather run in stream order with no host wait between them. */
+int rbgpu_bsi_values_device(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                            uint32_t key_hi, uint32_t *d_cols, uint64_t *d_vals, uint64_t cap, uint64_t *count);
+/* Roaring64BitmapSliceIndex.getValue / valueExist (:177-184, :284-286) for a batch of arbitrary columns (any
+ * order, duplicates allowed): values[i] = the value of columns[i], 0 where it is not in ebM; exists[i] = 1 / 0.
+ * Either output may be NULL.  rb_stats: kernel k_bsi_get, tasks = n. */
+int rbgpu_bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n,
+                         uint64_t *values, uint8_t *exists);
 /* RoaringBitmap.runOptimize (RoaringBitmap.java:2764-2775) of every bitmap of `in` into a new set:
  * each Array / Bitmap container becomes a Run when that is strictly smaller, each Run goes through
  * toEfficientContainer (ArrayContainer.java:1085-1099, BitmapContainer.java:1227-1246,

@@ -160,6 +160,10 @@ SIGNATURES = {
     "rbgpu_bsi_sum": (C.c_int, [_P, _P, _P, _U64P, _U64P]),
     "rbgpu_bsi_sum_sharded": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _U64P, _U64P]),
     "rbgpu_bsi_topk": (C.c_int, [_P, _P, _P, C.c_uint64, C.POINTER(_P)]),
+    "rbgpu_bsi_values": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, _U64P]),
+    "rbgpu_bsi_values_device": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          _U64P]),
+    "rbgpu_bsi_get_values": (C.c_int, [_P, _P, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rbgpu_generate_bsi_keys": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.POINTER(_P)]),
     "rbgpu_set_extract": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),

@@ -4,6 +4,9 @@
     setValue(columnId, value)        longlong/Roaring64BitmapSliceIndex.java:291-326
     compare(op, startOrValue, end, foundSet)              :460-503 (O'Neil, oNeilCompare :410-446)
     getExistenceBitmap / bitCount / runOptimize          :141-168
+    sum / topK                                            :559-594
+    getValue / valueExist / transpose                     :177-184, 284-286, 596-601
+    toPairList                                            buffer/BitSliceIndexBase.java:534-549
 
 The slices and the existence bitmap live in HBM as one DeviceSet (slices bA[0..n), then ebM) and a
 query runs as one fused MI355X pass per high key (librbgpu rbgpu_bsi_compare).  Values are
@@ -18,7 +21,7 @@ import numpy as np
 
 from . import _lib as L
 from .engine import DeviceSet, default_context
-from .roaring import RoaringBitmap
+from .roaring import Roaring64Bitmap, RoaringBitmap
 
 Operation = type("Operation", (), {"EQ": L.BSI_EQ, "NEQ": L.BSI_NEQ, "LE": L.BSI_LE, "LT": L.BSI_LT,
                                    "GE": L.BSI_GE, "GT": L.BSI_GT, "RANGE": L.BSI_RANGE})
@@ -107,13 +110,53 @@ class Roaring64BitmapSliceIndex:
         """topK(foundSet, k): the rows of foundSet holding the k largest values, by the reference's descent over the
         slices (a tie at the k-th value may leave fewer than k rows); None or an empty set gives an empty bitmap,
         k >= cardinality returns found_set itself (rbgpu_bsi_topk).  BitSliceIndexBase.topK (buffer/, with its
-        exact-k tie trimming) and transpose are not covered."""
+        exact-k tie trimming) is not covered; the rows' values come from getValues / toPairList."""
         if found_set is None or found_set.isEmpty():
             return RoaringBitmap()
         if k >= found_set.getCardinality():
             return found_set
         d = self._device()
         return RoaringBitmap(d.ctx.bsi_topk(d, found_set._set, k))
+
+    # ---- value read-back (Roaring64BitmapSliceIndex.java:127-136, 177-184, 284-286, 596-601;
+    # buffer/BitSliceIndexBase.java:534-549)
+    def _no_rows(self) -> bool:
+        return self._cols is not None and not self._cols
+
+    def getValues(self, column_ids) -> Tuple[np.ndarray, np.ndarray]:
+        """getValue for a batch of column ids (any order, duplicates allowed) -> (values uint64, exists bool): one
+        wave per column probes the 64 slices at once (rbgpu_bsi_get_values).  A column outside the existence
+        bitmap has value 0.  Values are the true unsigned values; the reference's valueAt accumulates `1 << i` in
+        an int and agrees for bitCount <= 31."""
+        c = np.asarray(column_ids, dtype=np.uint32).ravel()
+        if self._no_rows():
+            return np.zeros(len(c), np.uint64), np.zeros(len(c), bool)
+        d = self._device()
+        return d.ctx.bsi_get_values(d, c)
+
+    def getValue(self, column_id: int) -> Tuple[int, bool]:
+        """getValue(columnId) -> (value, exists): (0, False) for a column outside the existence bitmap."""
+        v, e = self.getValues([column_id])
+        return int(v[0]), bool(e[0])
+
+    def valueExist(self, column_id: int) -> bool:
+        return self.getValue(column_id)[1]
+
+    def toPairList(self, found_set: Optional[RoaringBitmap] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """toPairList() / toPairList(foundSet): the (columnId, value) pairs of the rows of the existence bitmap (AND
+        foundSet), ascending columnId — as two arrays (cols uint32, vals uint64), not a list of Pair objects: one
+        transposing pass per high key on the device (rbgpu_bsi_values)."""
+        if self._no_rows():
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint64)
+        d = self._device()
+        return d.ctx.bsi_values(d, found_set._set if found_set is not None else None)
+
+    def transpose(self, found_set: Optional[RoaringBitmap] = None) -> Roaring64Bitmap:
+        """transpose(foundSet): the distinct values of the rows of the existence bitmap (AND foundSet) as a
+        Roaring64Bitmap, the reference's re.add(getValue(x)) loop; an empty index or found set gives an empty
+        bitmap."""
+        _, vals = self.toPairList(found_set)
+        return Roaring64Bitmap.bitmapOf(np.unique(vals))
 
 
 RoaringBitmapSliceIndex = Roaring64BitmapSliceIndex  # the 32-bit index runs the same compare

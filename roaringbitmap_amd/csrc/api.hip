@@ -2033,6 +2033,39 @@ int rbgpu_bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found,
   return bsi_topk(ctx, bsi, found, k, out);
 }
 
+// the export's arguments (rbgpu_bsi_slice_counts' checks, and outputs that come as a pair)
+static int bsi_values_call(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                           uint32_t key_hi, uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count,
+                           bool host_dst) {
+  SETTLE(bsi, found);
+  if (!count) return fail(RB_EINVAL, "null count");
+  *count = 0;
+  int rc = check_bsi_agg(ctx, bsi, found);
+  if (rc) return rc;
+  if (key_lo > key_hi || key_hi > 65536) return fail(RB_EINVAL, "bad key range [%u, %u)", key_lo, key_hi);
+  if (!cols != !vals) return fail(RB_EINVAL, "cols and vals come together (both null: the count only)");
+  return bsi_values(ctx, bsi, found, key_lo, key_hi, cols, vals, cap, count, host_dst);
+}
+
+int rbgpu_bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
+                     uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count) {
+  return bsi_values_call(ctx, bsi, found, key_lo, key_hi, cols, vals, cap, count, true);
+}
+
+int rbgpu_bsi_values_device(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo,
+                            uint32_t key_hi, uint32_t *d_cols, uint64_t *d_vals, uint64_t cap, uint64_t *count) {
+  return bsi_values_call(ctx, bsi, found, key_lo, key_hi, d_cols, d_vals, cap, count, false);
+}
+
+int rbgpu_bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n, uint64_t *values,
+                         uint8_t *exists) {
+  SETTLE(bsi);
+  const int rc = check_bsi_agg(ctx, bsi, nullptr);
+  if (rc) return rc;
+  if (n && !columns) return fail(RB_EINVAL, "null columns");
+  return bsi_get_values(ctx, bsi, columns, n, values, exists);
+}
+
 int rbgpu_set_setup_stats(const rbgpu_set *s, double *ms, uint64_t *bytes) {
   if (!s || !ms || !bytes) return fail(RB_EINVAL, "null argument");
   *ms = s->derive_ms;

@@ -1249,6 +1249,424 @@ int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint6
   return done(RB_OK);
 }
 
+// ---------------------------------------------------------------- value read-back: toPairList and getValue
+// BitSliceIndexBase.toPairList(foundSet) (bsi/.../buffer/BitSliceIndexBase.java:534-549) and
+// Roaring64BitmapSliceIndex.getValue / valueExist (longlong/Roaring64BitmapSliceIndex.java:127-136, 177-184, 284-286).
+// The export is a 64 x 65536 bit-matrix transpose per high key restricted to the rows of F AND ebM; the lookup
+// probes the 64 slices of one column with the 64 lanes of a wave.
+
+// first index i of the sorted u16 array a[0, n) with a[i] >= x (n: none)
+__device__ __forceinline__ uint32_t lower_bound_u16(const uint16_t *a, uint32_t n, uint32_t x) {
+  uint32_t lo = 0;
+  while (n) {
+    const uint32_t h = n >> 1;
+    if (a[lo + h] < x) {
+      lo += h + 1;
+      n -= h + 1;
+    } else {
+      n = h;
+    }
+  }
+  return lo;
+}
+// first run i of the run list r[0, n) (start | length - 1 << 16; ascending, disjoint) that ends at or after x
+__device__ __forceinline__ uint32_t first_run_ending_from(const uint32_t *r, uint32_t n, uint32_t x) {
+  uint32_t lo = 0;
+  while (n) {
+    const uint32_t h = n >> 1, q = r[lo + h];
+    if ((q & 0xFFFF) + (q >> 16) < x) {
+      lo += h + 1;
+      n -= h + 1;
+    } else {
+      n = h;
+    }
+  }
+  return lo;
+}
+// x in the container?  Bitmap: one word; Array: a search over the values; Run: a search over the runs' ends, then
+// the start.  Straight from the payload, whatever its size (a Run of more than 2047 runs included).
+__device__ __forceinline__ bool container_has(int type, const uint8_t *p, uint32_t card, uint32_t nruns, uint32_t x) {
+  if (type == kBitmap) return (reinterpret_cast<const uint32_t *>(p)[x >> 5] >> (x & 31)) & 1u;
+  if (type == kArray) {
+    const uint16_t *a = reinterpret_cast<const uint16_t *>(p);
+    const uint32_t i = lower_bound_u16(a, card, x);
+    return i < card && a[i] == x;
+  }
+  const uint32_t *r = reinterpret_cast<const uint32_t *>(p);
+  const uint32_t i = first_run_ending_from(r, nruns, x);
+  return i < nruns && (r[i] & 0xFFFF) <= x;
+}
+// membership bits of the rows [base, base + 32) of an Array or Run container (base a multiple of 32): the values
+// and runs clipped to the word
+__device__ __forceinline__ uint32_t container_word(int type, const uint8_t *p, uint32_t card, uint32_t nruns,
+                                                   uint32_t base) {
+  uint32_t w = 0;
+  if (type == kArray) {
+    const uint16_t *a = reinterpret_cast<const uint16_t *>(p);
+    for (uint32_t i = lower_bound_u16(a, card, base); i < card; ++i) {
+      const uint32_t v = a[i];
+      if (v >= base + 32) break;
+      w |= 1u << (v - base);
+    }
+  } else {
+    const uint32_t *r = reinterpret_cast<const uint32_t *>(p);
+    for (uint32_t i = first_run_ending_from(r, nruns, base); i < nruns; ++i) {
+      const uint32_t q = r[i], s = q & 0xFFFF, e = s + (q >> 16);
+      if (s >= base + 32) break;
+      const uint32_t lo = max(s, base) - base, hi = min(e, base + 31) - base;
+      w |= (~0u >> (31 - hi)) & (~0u << lo);
+    }
+  }
+  return w;
+}
+
+// Phase A of the export: cnt[q] = |F AND ebM| at key klist[q].  F = ebM: the container's card from the metadata,
+// one thread per key, no payload read.  Else one wave per key stages ebM's container into registers, F's into LDS
+// and counts the AND; a key of F that ebM lacks counts 0.
+__global__ __launch_bounds__(256, 2) void k_bsi_values_count(SetView bsi, SetView fnd, int has_found,
+                                                             const int32_t *__restrict__ table, uint32_t nbits,
+                                                             const uint32_t *__restrict__ klist, uint32_t nk,
+                                                             uint64_t *__restrict__ cnt) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[4][2048];
+  if (!has_found) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q < nk) cnt[q] = bsi.card[table[(uint64_t)nbits * 65536 + klist[q]]]; // klist holds ebM's own keys
+    return;
+  }
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t q = blockIdx.x * 4 + wv;
+  if (q >= nk) return;
+  const uint32_t key = klist[q];
+  const int32_t ec = table[(uint64_t)nbits * 65536 + key];
+  uint32_t c = 0;
+  if (ec >= 0) { // wave-uniform
+    uint32_t *sS = lds[wv];
+    uint64_t e[kW];
+    stage_global(bsi, ec, sS, lane);
+    lds_read_words(sS, e, lane);
+    wave_lds_sync();
+    stage_global(fnd, table[(uint64_t)(nbits + 1) * 65536 + key], sS, lane); // present: the keys come from F
+    uint32_t p = 0;
+#pragma unroll
+    for (int j = 0; j < kW; ++j) p += (uint32_t)__popcll(e[j] & lds_word(sS, j, lane));
+    c = wave_sum_u32(p);
+  }
+  if (lane == 0) cnt[q] = c;
+}
+
+// 32 x 32 bit transpose in registers: a[i] bit r  ->  a[r] bit i (five rounds of masked block swaps)
+template <int J>
+__device__ __forceinline__ void transpose32_round(uint32_t (&a)[32], uint32_t m) {
+#pragma unroll
+  for (int k = 0; k < 32; ++k) {
+    if (k & J) continue;
+    const uint32_t t = ((a[k] >> J) ^ a[k + J]) & m;
+    a[k + J] ^= t;
+    a[k] ^= t << J;
+  }
+}
+__device__ __forceinline__ void transpose32(uint32_t (&a)[32]) {
+  transpose32_round<16>(a, 0x0000FFFFu);
+  transpose32_round<8>(a, 0x00FF00FFu);
+  transpose32_round<4>(a, 0x0F0F0F0Fu);
+  transpose32_round<2>(a, 0x33333333u);
+  transpose32_round<1>(a, 0x55555555u);
+}
+
+// The 32-row words of the slices S0 .. S0 + 31 for a tile (2048 rows: lane l <-> u32 word 64 * tile + l of the
+// container): a[i] = slice S0 + i's word.  A Bitmap slice's word is one coalesced 256-B read of its payload; the
+// words of the Array and Run slices are first built in the wave's tile buffer tbw[32][64] (container_word, only by
+// lanes that hold a row of F'); a slice without a container at the key is zero and its payload is not touched
+// (`dummy`: 64 readable words such a slice's lane reads instead).
+template <int S0>
+__device__ __forceinline__ void tile_words(uint32_t (&a)[32], const SliceDesc &d, const SetView &bsi, uint64_t pres,
+                                           uint64_t bm, uint32_t tile, uint32_t f, uint32_t *tbw,
+                                           const uint32_t *dummy, int lane) {
+  const uint32_t ph = (uint32_t)(pres >> S0), bh = (uint32_t)(bm >> S0);
+  uint32_t todo = ph & ~bh; // wave-uniform
+  while (todo) {
+    const int i = __builtin_ctz(todo);
+    todo &= todo - 1;
+    const Meta sm = d.meta(S0 + i);
+    tbw[i * 64 + lane] =
+        f ? container_word(sm.type, d.ptr(bsi, S0 + i), (uint32_t)sm.card, (uint32_t)sm.runs, (tile * 64 + lane) * 32) : 0u;
+  }
+  wave_lds_sync();
+  // 32 loads back to back with no branch between them (a branch per slice made the compiler wait for each load
+  // before it issued the next): a slice that is no Bitmap here reads the dummy word instead, which stays cached
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    const uint32_t *p = (bh >> i) & 1u ? reinterpret_cast<const uint32_t *>(d.ptr(bsi, S0 + i)) + tile * 64 : dummy;
+    a[i] = p[lane];
+  }
+  if (ph & ~bh) { // wave-uniform: some slice's word is in the tile buffer
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const uint32_t t = tbw[i * 64 + lane];
+      a[i] = (bh >> i) & 1u ? a[i] : (ph >> i) & 1u ? t : 0u;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) a[i] = (bh >> i) & 1u ? a[i] : 0u;
+  }
+  wave_lds_sync();
+}
+
+// The gather's per-wave LDS: the tile buffer of tile_words (32 x 64 words), then the store stage: kValStage
+// (value, column) slots, one pad slot per 32 (slot p at p + p / 32: the 64 lanes of a wave write ranks 32 apart, which
+// would otherwise share one bank).
+constexpr int kValStage = 1024, kValStagePad = kValStage + kValStage / 32, kValStageWords = 3 * kValStagePad;
+static_assert(kValStageWords >= 32 * 64, "the stage also holds tile_words' buffer");
+__device__ __forceinline__ uint32_t val_slot(uint32_t p) { return p + (p >> 5); }
+
+// Phase B of the export, the gather: one block per key of F.  Prologue: ebM's container and F's are staged into
+// two LDS images, F' = F AND ebM replaces the first and the 32 tiles' row counts go to LDS.  Then the four waves
+// take the tiles round-robin; a tile without a row of F' is skipped before any slice is touched.  A lane transposes
+// its own 32 x 32 bit blocks in registers (slices 0-31: the low dwords of its 32 rows, slices 32-63: the high
+// dwords, skipped when nbits <= 32); the rows of F' then go, compacted, to offs[q] + the rows of F' before them,
+// through an LDS stage so that a wave's stores are contiguous.
+// Nothing is written when the call's total offs[nk] exceeds cap.  No block waits for another: offs comes from the
+// launches before this one.
+__global__ __launch_bounds__(256, 2) void k_bsi_values(SetView bsi, SetView fnd, int has_found,
+                                                       const int32_t *__restrict__ table, uint32_t nbits,
+                                                       const uint32_t *__restrict__ klist, uint32_t nk,
+                                                       const uint64_t *__restrict__ offs, uint64_t cap,
+                                                       uint32_t *__restrict__ cols, uint64_t *__restrict__ vals,
+                                                       uint64_t *stats) {
+  __shared__ __attribute__((aligned(16))) uint32_t img[2][2048];
+  __shared__ __attribute__((aligned(16))) uint32_t wbuf[4][kValStageWords]; // per wave: tile words, then the stage
+  __shared__ uint32_t tcnt[32];
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t q = blockIdx.x;
+  if (offs[nk] > cap) return;
+  const uint32_t key = klist[q];
+  const uint64_t base = offs[q], lim = offs[q + 1];
+  const int32_t ec = table[(uint64_t)nbits * 65536 + key];
+  const int32_t fc = has_found ? table[(uint64_t)(nbits + 1) * 65536 + key] : -1;
+  SliceDesc d;
+  d.load(bsi, table, nbits, key, lane);
+  if (wv == 0) { // the call's counters: what the two phases read at this key, what this block writes
+    uint64_t inb = d.sc >= 0 && lim > base ? payload_bytes(d.st, d.scard, d.sruns) + 16 : 0;
+    inb = wave_sum_u64(inb);
+    if (ec >= 0) inb += payload_bytes(bsi.type[ec], bsi.card[ec], bsi.nruns[ec]) + 16;
+    if (fc >= 0) inb += payload_bytes(fnd.type[fc], fnd.card[fc], fnd.nruns[fc]) + 16;
+    if (lane == 0) {
+      const uint32_t stripe = q & (kStripes - 1);
+      atomicAdd((unsigned long long *)&stats[0 * kStripes + stripe], (unsigned long long)inb);
+      if (lim > base) {
+        atomicAdd((unsigned long long *)&stats[1 * kStripes + stripe], (unsigned long long)(12 * (lim - base)));
+        atomicAdd((unsigned long long *)&stats[7 * kStripes + stripe], (unsigned long long)(lim - base));
+      }
+    }
+  }
+  if (lim == base) return; // no row of F in ebM at this key (ebM may lack the key altogether)
+  if (wv == 0) stage_global(bsi, ec, img[0], lane);
+  else if (wv == 1 && has_found) stage_global(fnd, fc, img[1], lane);
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < 8; ++m) { // wave wv, round m: tile 4 m + wv, lane <-> word
+    const int j = 256 * m + (int)threadIdx.x;
+    const uint32_t f = img[0][j] & (has_found ? img[1][j] : ~0u);
+    img[0][j] = f;
+    const uint32_t c = wave_sum_u32((uint32_t)__popc(f));
+    if (lane == 0) tcnt[4 * m + wv] = c;
+  }
+  __syncthreads();
+  // exclusive prefix of the tiles' row counts, lane t <-> tile t (every wave computes its own copy)
+  const uint32_t tc = lane < 32 ? tcnt[lane] : 0u;
+  const uint32_t tbase = wave_scan_u32(tc, lane) - tc;
+  const uint64_t pres = __ballot(d.sc >= 0), bm = __ballot(d.sc >= 0 && d.st == kBitmap);
+  uint32_t *tbw = wbuf[wv];
+  const uint32_t *dummy = reinterpret_cast<const uint32_t *>(table); // 64 readable words for tile_words
+  for (uint32_t tile = (uint32_t)wv; tile < 32; tile += 4) {
+    if (!readlane(tc, (int)tile)) continue;
+    const uint32_t f = img[0][tile * 64 + lane];
+    const uint32_t n = (uint32_t)__popc(f);
+    uint32_t lo[32], hi[32];
+    tile_words<0>(lo, d, bsi, pres, bm, tile, f, tbw, dummy, lane);
+    transpose32(lo);
+    if (nbits > 32) {
+      tile_words<32>(hi, d, bsi, pres, bm, tile, f, tbw, dummy, lane);
+      transpose32(hi);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 32; ++r) hi[r] = 0;
+    }
+    // ---- the tile's rows leave through the wave's LDS stage, kValStage ranks at a time: a lane's rows are
+    // consecutive ranks, so direct stores would put the 64 lanes of one instruction on 64 different lines
+    const uint32_t col0 = (key << 16) | ((tile * 64 + lane) * 32);
+    const uint32_t ntile = readlane(tc, (int)tile), rank0 = wave_scan_u32(n, lane) - n;
+    const uint64_t tpos = base + readlane(tbase, (int)tile);
+    uint64_t *sv = reinterpret_cast<uint64_t *>(tbw);
+    uint32_t *sc = tbw + 2 * kValStagePad;
+    for (uint32_t w0 = 0; w0 < ntile; w0 += kValStage) {
+      uint32_t p = rank0 - w0; // this window's slots are the ranks w0 .. w0 + kValStage - 1 (unsigned compare)
+#pragma unroll
+      for (int r = 0; r < 32; ++r) {
+        if ((f >> r) & 1u) {
+          if (p < (uint32_t)kValStage) {
+            sv[val_slot(p)] = pack2(lo[r], hi[r]);
+            sc[val_slot(p)] = col0 + r;
+          }
+          ++p;
+        }
+      }
+      wave_lds_sync();
+      const uint32_t nw = min(ntile - w0, (uint32_t)kValStage);
+      for (uint32_t i = (uint32_t)lane; i < nw; i += 64) {
+        const uint64_t g = tpos + w0 + i;
+        if (g < lim) { // holds when the metadata's card matches the payload
+          vals[g] = sv[val_slot(i)];
+          cols[g] = sc[val_slot(i)];
+        }
+      }
+      wave_lds_sync();
+    }
+  }
+}
+
+// getValue / valueExist of a batch of columns: one wave per query, grid-stride, four queries per block.  ebM's
+// container is probed first (wave-uniform); then lane i probes slice i and one ballot is the 64-bit value.
+__global__ __launch_bounds__(256, 2) void k_bsi_get(SetView bsi, const int32_t *__restrict__ table, uint32_t nbits,
+                                                    const uint32_t *__restrict__ columns, uint64_t n,
+                                                    uint64_t *__restrict__ values, uint8_t *__restrict__ exists) {
+  const int lane = lane_id();
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (uint64_t q = (uint64_t)blockIdx.x * 4 + wv; q < n; q += (uint64_t)gridDim.x * 4) {
+    const uint32_t col = columns[q], key = col >> 16, x = col & 0xFFFF;
+    const int32_t ec = table[(uint64_t)nbits * 65536 + key];
+    const bool e = ec >= 0 && container_has(bsi.type[ec], bsi.payload + bsi.off[ec], bsi.card[ec], bsi.nruns[ec], x);
+    bool hit = false;
+    if (e && lane < (int)nbits) {
+      const int32_t sc = table[(uint64_t)lane * 65536 + key];
+      if (sc >= 0) hit = container_has(bsi.type[sc], bsi.payload + bsi.off[sc], bsi.card[sc], bsi.nruns[sc], x);
+    }
+    const uint64_t v = __ballot(hit);
+    if (lane == 0) {
+      if (values) values[q] = v;
+      if (exists) exists[q] = e ? 1 : 0;
+    }
+  }
+}
+
+// the export's host side; host_dst: cols / vals are host memory (gathered into pool buffers and copied out)
+int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
+               uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count, bool host_dst) {
+  const uint32_t nbits = bsi->nb - 1;
+  hipStream_t st = ctx->stream;
+  const bool count_only = !cols && !vals;
+  *count = 0;
+  stats_begin(ctx);
+  BsiKeys ks;
+  int rc = bsi_keys(ctx, bsi, nbits, found, key_lo, key_hi, ks);
+  if (rc) return rc;
+  const uint32_t nk = ks.nk;
+  uint64_t *cnt = nullptr, *offs = nullptr, *tmp = nullptr;
+  uint32_t *d_cols = host_dst ? nullptr : cols;
+  uint64_t *d_vals = host_dst ? nullptr : vals;
+  auto done = [&](int r) {
+    for (void *p : {(void *)cnt, (void *)offs, (void *)tmp}) ctx->pool.release(p);
+    if (host_dst) {
+      ctx->pool.release(d_cols);
+      ctx->pool.release(d_vals);
+    }
+    ks.release(ctx);
+    return r;
+  };
+  if (ctx->pool.alloc((void **)&cnt, (nk + 1ull) * 8) || ctx->pool.alloc((void **)&offs, (nk + 2ull) * 8) ||
+      ctx->pool.alloc((void **)&tmp, (scan_tmp_words(nk) + 1) * 8))
+    return done(fail(RB_ENOMEM, "bsi values: counts of %u keys", nk));
+  const SetView bv = bsi->view(), fv = found ? found->view() : bv;
+  const int hf = found != nullptr;
+  auto gather = [&]() { // phase B, between its own events
+    hipError_t e = hipEventRecord(ctx->ev[3], st);
+    if (e == hipSuccess) {
+      k_bsi_values<<<nk, 256, 0, st>>>(bv, fv, hf, bsi->bsi_table, nbits, ks.d_klist, nk, offs, cap, d_cols, d_vals,
+                                       ctx->d_stats);
+      e = hipEventRecord(ctx->ev[4], st);
+    }
+    return e;
+  };
+  // ---- phase A: the keys' row counts and their exclusive scan (offs[nk] = the call's count)
+  hipError_t e = hipEventRecord(ctx->ev[1], st);
+  if (e == hipSuccess && nk) {
+    k_bsi_values_count<<<hf ? nblk(nk, 4) : nblk(nk, 256), 256, 0, st>>>(bv, fv, hf, bsi->bsi_table, nbits, ks.d_klist,
+                                                                        nk, cnt);
+    scan_exclusive(cnt, offs, nk, tmp, st);
+  }
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], st);
+  // device outputs: phase B follows in stream order with no host wait (it writes nothing when the count exceeds cap)
+  bool gathered = false;
+  if (e == hipSuccess && nk && !count_only && !host_dst) {
+    e = gather();
+    gathered = true;
+  }
+  // the call's one read-back before any host copy
+  uint64_t total = 0;
+  if (e == hipSuccess && nk) {
+    e = hipMemcpyAsync(ctx->h_pinned, offs + nk, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipGetLastError();
+    total = ctx->h_pinned[0];
+  }
+  if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi values failed: %s", hipGetErrorString(e)));
+  *count = total;
+  if (!count_only && total > cap)
+    return done(fail(RB_EINVAL, "bsi values: %llu pairs exceed the capacity %llu", (unsigned long long)total,
+                     (unsigned long long)cap));
+  if (!count_only && host_dst && total) { // host outputs: the buffers take the count the read-back gave
+    if (ctx->pool.alloc((void **)&d_cols, total * 4) || ctx->pool.alloc((void **)&d_vals, total * 8))
+      return done(fail(RB_ENOMEM, "bsi values: %llu pairs", (unsigned long long)total));
+    e = gather();
+    gathered = true;
+    if (e == hipSuccess) e = hipMemcpyAsync(cols, d_cols, total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(vals, d_vals, total * 8, hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi values failed: %s", hipGetErrorString(e)));
+  }
+  const KernelSpan spans[2] = {{"k_bsi_values", 0, 1, nk, ctx->ev[3], ctx->ev[4]},
+                               {"k_bsi_values_count", -1, -1, nk, ctx->ev[1], ctx->ev[2]}};
+  rc = gathered ? stats_end(ctx, nk, 0, spans, 2) : stats_end(ctx, nk, 0, spans + 1, 1);
+  if (!rc && gathered) { // the gather is the call's main kernel, whichever phase took longer
+    rb_stats &s = ctx->last;
+    s.main_kernel_ms = s.kernel_ms[0];
+    s.main_kernel_bytes = s.kernel_bytes[0];
+    std::snprintf(s.main_kernel, sizeof s.main_kernel, "%s", s.kernel_name[0]);
+  }
+  return done(rc);
+}
+
+int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n, uint64_t *values,
+                   uint8_t *exists) {
+  const uint32_t nbits = bsi->nb - 1;
+  hipStream_t st = ctx->stream;
+  stats_begin(ctx);
+  int rc = ensure_bsi_tables(ctx, bsi, nbits);
+  if (rc) return rc;
+  uint32_t *d_c = nullptr;
+  uint64_t *d_v = nullptr;
+  uint8_t *d_e = nullptr;
+  auto done = [&](int r) {
+    for (void *p : {(void *)d_c, (void *)d_v, (void *)d_e}) ctx->pool.release(p);
+    return r;
+  };
+  if (n && (ctx->pool.alloc((void **)&d_c, n * 4) || (values && ctx->pool.alloc((void **)&d_v, n * 8)) ||
+            (exists && ctx->pool.alloc((void **)&d_e, n))))
+    return done(fail(RB_ENOMEM, "bsi lookups of %llu columns", (unsigned long long)n));
+  hipError_t e = n ? hipMemcpyAsync(d_c, columns, n * 4, hipMemcpyHostToDevice, st) : hipSuccess;
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
+  if (e == hipSuccess && n)
+    k_bsi_get<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 4096), 256, 0, st>>>(bsi->view(), bsi->bsi_table, nbits, d_c,
+                                                                              n, d_v, d_e);
+  if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], st);
+  if (e == hipSuccess && n && values) e = hipMemcpyAsync(values, d_v, n * 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n && exists) e = hipMemcpyAsync(exists, d_e, n, hipMemcpyDeviceToHost, st);
+  if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi lookups failed: %s", hipGetErrorString(e)));
+  const KernelSpan spans[1] = {{"k_bsi_get", -1, -1, n}};
+  return done(stats_end(ctx, n, 0, spans, n ? 1 : 0));
+}
+
 // this file's code object, loaded at context creation (warm_code_objects, api.hip)
 __global__ void k_warm_bsi() {}
 void warm_bsi(hipStream_t st) { k_warm_bsi<<<1, 64, 0, st>>>(); }

@@ -332,6 +332,13 @@ int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, ui
 int bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
                      uint64_t *counts);
 int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint64_t k, rbgpu_set **out);
+// bsi.hip, the value read-back: the (column, value) pairs of the rows of F AND ebM over the high keys in
+// [key_lo, key_hi) (host_dst: cols / vals are host memory, else device memory; both null: the count only), and
+// getValue / valueExist of a batch of columns (host arrays; values or exists may be null)
+int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint32_t key_lo, uint32_t key_hi,
+               uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count, bool host_dst);
+int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n, uint64_t *values,
+                   uint8_t *exists);
 // api.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
 int set_key_subset(const rbgpu_set *s, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
 int set_gather(const rbgpu_set *s, const uint32_t *idx, uint32_t n, rbgpu_set **out);

@@ -596,6 +596,42 @@ class Context:
                                        C.byref(out)))
         return DeviceSet(self, out.value)
 
+    def bsi_values(self, bsi: DeviceSet, found: Optional[DeviceSet] = None,
+                   key_range=None) -> Tuple[np.ndarray, np.ndarray]:
+        """BitSliceIndexBase.toPairList(foundSet) over a device BSI: (cols uint32, vals uint64) of the rows of
+        ebM AND found (found None: ebM), ascending cols, over the high keys of key_range (default: all)
+        (rbgpu_bsi_values: a count-only call sizes the arrays, a second call fills them)."""
+        lo, hi = key_range if key_range is not None else (0, 65536)
+        f = found.h if found is not None else None
+        n = C.c_uint64()
+        L.check(L.lib().rbgpu_bsi_values(self.h, bsi.h, f, int(lo), int(hi), None, None, 0, C.byref(n)))
+        cols, vals = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint64)
+        if n.value:
+            L.check(L.lib().rbgpu_bsi_values(self.h, bsi.h, f, int(lo), int(hi), cols.ctypes.data, vals.ctypes.data,
+                                             n.value, C.byref(n)))
+        return cols, vals
+
+    def bsi_values_device(self, bsi: DeviceSet, cols_ptr: int, vals_ptr: int, cap: int,
+                          found: Optional[DeviceSet] = None, key_range=None) -> int:
+        """The same pairs written by the GPU into device memory at cols_ptr (uint32[cap]) and vals_ptr
+        (uint64[cap]); returns the count (rbgpu_bsi_values_device).  cols_ptr = vals_ptr = 0: the count only; a
+        count above cap raises InvalidArgument and writes nothing."""
+        lo, hi = key_range if key_range is not None else (0, 65536)
+        n = C.c_uint64()
+        L.check(L.lib().rbgpu_bsi_values_device(self.h, bsi.h, found.h if found is not None else None, int(lo),
+                                                int(hi), C.c_void_p(cols_ptr or None), C.c_void_p(vals_ptr or None),
+                                                int(cap), C.byref(n)))
+        return int(n.value)
+
+    def bsi_get_values(self, bsi: DeviceSet, columns) -> Tuple[np.ndarray, np.ndarray]:
+        """Roaring64BitmapSliceIndex.getValue / valueExist for a batch of columns (any order, duplicates allowed):
+        (values uint64, exists bool); a column outside ebM has value 0 (rbgpu_bsi_get_values)."""
+        c = np.ascontiguousarray(np.asarray(columns, dtype=np.uint32))
+        vals, ex = np.zeros(len(c), np.uint64), np.zeros(len(c), np.uint8)
+        L.check(L.lib().rbgpu_bsi_get_values(self.h, bsi.h, c.ctypes.data if len(c) else None, len(c),
+                                             vals.ctypes.data if len(c) else None, ex.ctypes.data if len(c) else None))
+        return vals, ex.astype(bool)
+
     def generate_bsi(self, nslices: int, nrows: int, seed: int = 42, key_range=None) -> DeviceSet:
         """The synthetic BSI of SURVEY §8d config 5, or its [lo, hi) key-range shard."""
         a = C.c_void_p()
