@@ -1227,7 +1227,9 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       // ---- phase 1: stage X (filter; kBits: the other operand) or store the clone (copy)
       if (tc.kind == kFilter || tc.kind == kBits) {
         if (tc.bigq) stage_big_runs(tc.pq, tc.rq, s, fresh(lane)); // only a Run payload exceeds 8 KiB
-        else stage_from_chunks(tc.tq, qq, tc.cq, tc.rq, s, fresh(lane));
+        // a filter probes a Run X by parity on the carry-folded toggle image; kBits ORs membership words (and
+        // stage_big_runs always leaves those: the filter below picks its probe by the same condition)
+        else stage_from_chunks(tc.tq, qq, tc.cq, tc.rq, s, fresh(lane), tc.kind == kFilter);
       } else if (!CARD_ONLY) {
         if (tc.bigp) {
           copy_payload(tc.pp, dst, tc.pbytes, fresh(lane), qq); // Q's registers: a copy has no Q
@@ -1250,8 +1252,10 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       if (tc.kind == kFilter) {
         uint16_t *o = CARD_ONLY ? nullptr : reinterpret_cast<uint16_t *>(dst);
         uint4 *tb = tbuf[ROLE == kRoleLight ? wv : 0];
-        c = OP == RB_ANDNOT ? filter_rows_linear<true, !CARD_ONLY>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane))
-                            : filter_rows_linear<false, !CARD_ONLY>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane));
+        constexpr bool kNeg = OP == RB_ANDNOT;
+        if (tc.tq == kRun && !tc.bigq) // wave-uniform: the image staged above is the folded one
+          c = filter_rows_linear<kNeg, !CARD_ONLY, true>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane));
+        else c = filter_rows_linear<kNeg, !CARD_ONLY, false>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane));
         ty = c ? kArray : kEmpty;
       } else if (tc.kind == kBits) {
         // ---- OR into the large Bitmap P (bits_task): the rows ORed and counted first, then stored — as the

@@ -129,31 +129,32 @@ __device__ __forceinline__ void lds_write_words(uint32_t *s, const uint64_t (&w)
                                    (uint32_t)(w[2 * k + 1] >> 32));
 }
 
-// OR one lane's chunk of sorted values (n <= 8) into the LDS bitmap: a segmented OR over runs of
-// equal word index in registers, then one ds_or per value, carrying the group's mask at the group's
-// last value and 0 elsewhere (an OR of 0 changes nothing).  No value-dependent branch: the earlier
-// form branched per value on "new word?", which cost ~16 SALU exec-mask instructions per value.
-// Values past n OR 0 into the word of the last live value.
+// OR one lane's chunk of distinct values (n <= 8) into the LDS bitmap: one single-bit ds_or per
+// value.  Distinct single bits commute under OR and under XOR, so the image does not depend on the
+// order or on which lanes share a word, and nothing is carried from value to value (the earlier
+// form folded the values of one word into a group mask first, ~7 VALU per value, and still issued
+// the 8 atomics).  No value-dependent branch.  A slot past n sends 0 to whatever word its bits
+// name: the word index keeps 11 bits, so it lies inside the image whatever the slot holds (the
+// pad of a payload's last 16 bytes, or the end+1 = 65536 of a container's last run).
 template <bool XOR = false> // XOR: ds_xor instead of ds_or (a second operand into the same image)
 __device__ __forceinline__ void or_chunk_values(const uint32_t (&x)[8], int n, uint32_t *s) {
-  uint32_t acc = 0, prev = x[0] >> 5;
-  const uint32_t lastw = x[n - 1 < 7 ? n - 1 : 7] >> 5;
+  typedef __attribute__((address_space(3))) uint32_t lds_u32;
+  lds_u32 *ls = (lds_u32 *)s;
+  const uint32_t live = (1u << n) - 1u; // bit i: slot i holds a value (i < n)
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const bool live = i < n;
-    const uint32_t wi = live ? x[i] >> 5 : lastw;
-    acc = (wi == prev ? acc : 0u) | (live ? 1u << (x[i] & 31) : 0u);
-    prev = wi;
-    // past n the last group's mask is re-emitted: harmless for ds_or, not for ds_xor
-    const bool last = (!XOR || live) && (i == 7 || i + 1 >= n || (x[i + 1] >> 5) != wi);
-    if (XOR) atomicXor(&s[wi], last ? acc : 0u);
-    else atomicOr(&s[wi], last ? acc : 0u);
+    // i < n ? 1 << (x & 31) : 0 as v_bfe + v_lshlrev (the shift reads the low 5 bits of x), the word's
+    // address as v_bfe + v_lshl_add (as in filter_rows_linear: the compiler's own lowering takes three)
+    uint32_t wi;
+    asm("v_bfe_u32 %0, %1, 5, 11" : "=v"(wi) : "v"(x[i]));
+    const uint32_t bit = __builtin_amdgcn_ubfe(live, (uint32_t)i, 1u) << (x[i] & 31);
+    if (XOR) __hip_atomic_fetch_xor(ls + wi, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_fetch_or(ls + wi, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   }
 }
 
 // OR the values of a sorted u16 array (payload 16-B aligned) into the LDS bitmap `s`.  Each lane
-// takes 8 consecutive values per 16-B load (coalesced), folds them per 32-bit word and issues
-// one ds_or per word.
+// takes 8 consecutive values per 16-B load (coalesced) and issues one single-bit ds_or per value.
 __device__ __forceinline__ void lds_or_array(const uint16_t *vals, int card, uint32_t *s, int lane) {
   const uint4 *v4 = reinterpret_cast<const uint4 *>(vals);
   const int nchunks = (card + 7) >> 3;
@@ -233,6 +234,37 @@ __device__ __forceinline__ void toggles_to_words_lds(uint32_t *s, int lane) {
     const uint64_t w0 = prefix_xor64(pack2(v.x, v.y)) ^ (c0 ? ~0ull : 0ull);
     const uint64_t w1 = prefix_xor64(pack2(v.z, v.w)) ^ (c1 ? ~0ull : 0ull);
     s4[k * 64 + lane] = make_uint4((uint32_t)w0, (uint32_t)(w0 >> 32), (uint32_t)w1, (uint32_t)(w1 >> 32));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// Toggle image -> carry-folded toggle image, in place: the parity of all toggles below a 32-bit word
+// (its carry-in) is XORed into the word's bit 0.  With t' = t ^ c, membership of bit b of the word is
+// c ^ parity(t & bits 0..b) = parity(t' & bits 0..b) (bit 0 lies in every such mask), which a reader
+// that only probes positions takes as popc(t' << (31 - b)) & 1 (filter_rows_linear<.., PARITY>) — no
+// membership words, no 64-bit prefix-xor.  The carry walks the lane's four dwords of a row by the
+// parity of the folded word before it: popc(t') & 1 = parity(t) ^ c.  Row and lane carries as in
+// toggles_to_words_lds.
+__device__ __forceinline__ void toggles_fold_carry_lds(uint32_t *s, int lane) {
+  uint4 *s4 = reinterpret_cast<uint4 *>(s);
+  uint32_t q = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint4 v = s4[k * 64 + lane];
+    q |= ((__popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w)) & 1u) << k;
+  }
+  const uint32_t incl = wave_xscan_xor(q, lane);
+  const uint32_t excl = incl ^ q;
+  const uint32_t tot = readlane(incl, 63);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    uint4 v = s4[k * 64 + lane];
+    const uint32_t rowc = __popc(tot & ((1u << k) - 1)) & 1;
+    v.x ^= rowc ^ ((excl >> k) & 1);
+    v.y ^= __popc(v.x) & 1;
+    v.z ^= __popc(v.y) & 1;
+    v.w ^= __popc(v.z) & 1;
+    s4[k * 64 + lane] = v;
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -376,7 +408,9 @@ constexpr int kStageVals = kStageRing + 64; // + one dummy slot per lane
 // so a kept value's slot is (pending + mbcnt) with no wrap — mbcnt adds the pending count itself.
 // ~8 VALU per 64 probed values (a ring with modulo took ~15, ISA count).  Pending values stay < 8 + 512.
 // A last row with <= 256 values skips its empty second half.
-template <bool NEGATE, bool STORE>
+// PARITY: `s` is a carry-folded toggle image (toggles_fold_carry_lds) instead of membership words; a value's
+// membership is the parity of its word's bits at or below it (three more VALU per probe than the bit extract).
+template <bool NEGATE, bool STORE, bool PARITY = false>
 __device__ __forceinline__ int filter_rows_linear(const uint4 (&fq)[8], int nf, const uint32_t *s, uint16_t *ob,
                                                   uint4 *tb, uint16_t *out, int lane) {
   static_assert(7 + 512 <= kStageRing, "every slot (pending < 8, + < 512 of a row) lies below the dummies");
@@ -409,7 +443,9 @@ __device__ __forceinline__ int filter_rows_linear(const uint4 (&fq)[8], int nf, 
         for (int k = 0; k < 4; ++k) {
           // membership bit (v_bfe reads the offset's low 5 bits), its ballot as an integer compare (no
           // bool round trip), lanes past the half masked off in scalar registers
-          const uint32_t bit = __builtin_amdgcn_ubfe(m[k], y[k], 1u);
+          // (PARITY: the word shifted so that the value's bit is the top one — v_lshlrev reads the low 5 bits
+          // of ~y, i.e. 31 - (y & 31) — then the parity of what is left)
+          const uint32_t bit = PARITY ? (uint32_t)__popc(m[k] << (~y[k] & 31u)) & 1u : __builtin_amdgcn_ubfe(m[k], y[k], 1u);
           uint64_t b = __builtin_amdgcn_uicmp(bit, 0u, NEGATE ? 32 : 33); // ICMP_EQ / ICMP_NE
           const int lim = nh - 64 * k;
           if (lim < 64) b &= lim > 0 ? (1ull << lim) - 1ull : 0ull;
@@ -479,9 +515,11 @@ __device__ __forceinline__ void stage_run_toggles(const uint4 (&q)[8], uint32_t 
 }
 
 // Membership image in LDS from a register-preloaded payload (Array <= 4096 values, Run <= 2047
-// runs, Bitmap 8 KiB — i.e. every canonical container whose payload fits 8 KiB).
+// runs, Bitmap 8 KiB — i.e. every canonical container whose payload fits 8 KiB).  `fold_runs`
+// (wave-uniform): a Run is left as its carry-folded toggle image (toggles_fold_carry_lds), for a
+// reader that probes by parity; Arrays and Bitmaps are membership words either way.
 __device__ __forceinline__ void stage_from_chunks(int type, const uint4 (&q)[8], uint32_t card, uint32_t nruns,
-                                                  uint32_t *s, int lane) {
+                                                  uint32_t *s, int lane, bool fold_runs = false) {
   uint4 *s4 = reinterpret_cast<uint4 *>(s);
   if (type == kBitmap) {
 #pragma unroll
@@ -502,9 +540,8 @@ __device__ __forceinline__ void stage_from_chunks(int type, const uint4 (&q)[8],
       }
     } else {
       // A lane's chunk of 4 canonical runs gives 8 strictly increasing toggle positions (start,
-      // end+1; runs are sorted and non-adjacent), so they group by word exactly like sorted Array
-      // values: only the first and last word of a chunk can be shared with a neighbour chunk, and
-      // within a word the toggles are distinct bits (OR == XOR).  An end+1 of 65536 is dropped.
+      // end+1; runs are sorted and non-adjacent): distinct bits over the whole container, so they
+      // are staged like Array values (OR == XOR).  An end+1 of 65536 is dropped.
       const int nchunks = (int)((nruns + 3) >> 2);
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -525,7 +562,8 @@ __device__ __forceinline__ void stage_from_chunks(int type, const uint4 (&q)[8],
         }
       }
       wave_lds_sync();
-      toggles_to_words_lds(s, lane);
+      if (fold_runs) toggles_fold_carry_lds(s, lane);
+      else toggles_to_words_lds(s, lane);
     }
   }
   wave_lds_sync();
