@@ -28,9 +28,12 @@ def run_lists():
 
 
 def big_run_lists():
-    """More than 2047 runs: a payload over 8 KiB, staged straight from global memory."""
+    """More than 2047 runs, which no runOptimize'd bitmap holds.  2048 runs are exactly 8 KiB in the set layout (the
+    run count lives in the metadata): the last size staged through the registers.  From 2049 runs on the payload
+    is over 8 KiB and staged straight from global memory."""
     return [
         ("big2048", [(3 + 31 * i, 3 + 31 * i + 4) for i in range(2048)]),
+        ("big2049", [(1 + 31 * i, 1 + 31 * i + 5) for i in range(2049)]),
         ("big3000_to_end", [(21 * i, 21 * i + 6) for i in range(2999)] + [(65000, 65535)]),
         ("big_random5000", random_runs(5000, 77)),
     ]

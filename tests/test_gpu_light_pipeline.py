@@ -63,8 +63,9 @@ def _check(ctx, oracle, op, sa, sb, ai, bi, refs_a, refs_b, order, what):
 
 # ------------------------------------------------------------------ 1. row boundaries of F
 def _x_zoo():
-    """(name, values, canonical): the other operand X of the filter.  The last is a Run of more than 2047 runs,
-    which no runOptimize'd bitmap holds (a Bitmap is smaller): it is uploaded as that container type."""
+    """(name, values, canonical): the other operand X of the filter.  The last two are Runs of more than 2047 runs,
+    which no runOptimize'd bitmap holds (a Bitmap is smaller): they are uploaded as that container type.  2049
+    runs is the first size over 8 KiB (2048 runs are exactly 8192 B: still staged through the registers)."""
     rng = np.random.default_rng(11)
     return [
         ("bitmap", np.sort(rng.choice(65536, 30000, replace=False)).astype(np.uint32), True),
@@ -72,7 +73,8 @@ def _x_zoo():
         ("array4096", np.sort(rng.choice(65536, 4096, replace=False)).astype(np.uint32), True),
         ("run1", r(9000, 39000), True),
         ("run2047", _runs(2047, 9, 32), True),     # 18423 values in 8190 B: a Run
-        ("run3000", _runs(3000, 7, 21), False),    # 12002 B: staged straight from global memory (bigq)
+        ("run2049", _runs(2049, 7, 31), False),    # 8196 B: the first size staged from global memory (bigq)
+        ("run3000", _runs(3000, 7, 21), False),    # 12000 B
     ]
 
 
@@ -100,28 +102,30 @@ def _f_sets(xvals, rng):
 
 @pytest.fixture(scope="module")
 def rows(ctx, oracle):
-    """One set of canonical bitmaps (every F, every canonical X; one key each) and one holding the big Run; the
+    """One set of canonical bitmaps (every F, every canonical X; one key each) and one holding the big Runs; the
     unique (F, X) pairs as indices; the oracle's bitmaps."""
     rng = np.random.default_rng(5)
-    vals, pairs_canon, pairs_big, big = [], [], [], None
+    vals, pairs_canon, pairs_big, big = [], [], [], []
     for name, xv, canon in _x_zoo():
         fs = _f_sets(xv, rng)
         if canon:
             xi = len(vals)
             vals.append(xv)
         else:
-            big = xv
+            xi = len(big)
+            big.append(xv)
         for f in fs:
-            (pairs_canon if canon else pairs_big).append((len(vals), xi if canon else 0))
+            (pairs_canon if canon else pairs_big).append((len(vals), xi))
             vals.append(f)
     s = ctx.upload_values(vals, run_optimize=True)
     h = s.download()
     for fi, _ in pairs_canon + pairs_big:  # every F is one Array container
         assert int(h.begin[fi + 1] - h.begin[fi]) == 1 and int(h.type[int(h.begin[fi])]) == ARRAY
-    sb = ctx.upload_soa(one_container_soa([(RUN, big)]))
-    assert int(sb.download().type[0]) == RUN and int(sb.download().nruns[0]) > 2047
+    sb = ctx.upload_soa(one_container_soa([(RUN, v) for v in big]))
+    hb = sb.download()
+    assert [int(t) for t in hb.type] == [RUN] * len(big) and [int(n) for n in hb.nruns] == [2049, 3000]
     refs = [oracle.RefBitmap.deserialize(x) for x in s.serialize()]
-    refs_big = [oracle_bitmap(oracle, RUN, big)]
+    refs_big = [oracle_bitmap(oracle, RUN, v) for v in big]
     yield {"s": s, "sb": sb, "refs": refs, "refs_big": refs_big,
            "canon": np.array(pairs_canon, np.int64), "big": np.array(pairs_big, np.int64)}
     s.close()
@@ -158,7 +162,8 @@ def copies(ctx, oracle):
     h = s.download()
     for i in range(2, 6):
         assert int(h.type[int(h.begin[i])]) == RUN and 1792 <= int(h.nruns[int(h.begin[i])]) <= 2047
-    big = [_runs(2048, 5, 31), _runs(5000, 2, 13), r(0, 65536, 2)]  # 8194 B, 20002 B and 131074 B
+    # payloads of 8192 B (2048 runs: the last size copied through the registers), 8196 B, 20000 B and 131072 B
+    big = [_runs(2048, 5, 31), _runs(2049, 5, 31), _runs(5000, 2, 13), r(0, 65536, 2)]
     sb = ctx.upload_soa(one_container_soa([(RUN, v) for v in big]))
     refs = [oracle.RefBitmap.deserialize(x) for x in s.serialize()]
     refs_big = [oracle_bitmap(oracle, RUN, v) for v in big]

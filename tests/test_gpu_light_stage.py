@@ -6,7 +6,8 @@ pipeline, byte-exact (RoaringFormatSpec) against the oracle with rbgpu_pairwise_
   2. Array X shapes: all values in one 32-bit word, 0..4095 (adjacent lanes hit the same word), 31/32/63/64/65535;
   3. a Run X (the run lists of light_stage_cases.py) probed at start-1, start, end, end+1 of every run and at
      random positions: the filter reads the carry-folded toggle image by parity;
-  4. a Run X of more than 2047 runs (staged from global memory as membership words) with the same probes;
+  4. a Run X of more than 2047 runs (2048 runs, exactly 8 KiB, are the last size staged through the registers;
+     from 2049 on it is staged from global memory as membership words) with the same probes;
   5. paths that must still see membership words: OR of a Run or Array into a large Bitmap, and the register
      path's Run AND Bitmap, Run OR Array, Run XOR Run;
   6. all of 1-4 in one batch above the queued, concurrent launch threshold (65,536 tasks).
