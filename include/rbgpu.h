@@ -207,6 +207,41 @@ int rbgpu_set_range_counts(const rbgpu_set *set, const uint32_t *members, uint32
  * n_containers / payload_bytes, allocate, call again to fill. */
 int rbgpu_set_download(const rbgpu_set *set, uint32_t first, uint32_t count, rb_soa *soa);
 
+/* ---- value read-out (the value-side entry points of RoaringBitmap) --------------------
+ * The members themselves, decoded on the device from the containers where they lie: no payload crosses to the
+ * host.  The calls run on the set's context; a pending asynchronous result is waited for first.  The answers
+ * do not depend on the container types.  On first use a set gains one derived index, the exclusive prefix of its
+ * containers' cardinalities (8 B per container, freed with the set; counted in rbgpu_set_setup_stats, not in
+ * rbgpu_set_setup_parts).  Bad arguments — a range past the set, a bitmap[i] >= the set's bitmap count, a null
+ * query or output array with n > 0 — give RB_EINVAL before any launch; n == 0, count == 0 and bitmaps without
+ * containers are legal. */
+/* RoaringBitmap.toArray (RoaringBitmap.java:3224) of bitmaps [first, first+count): their values ascending, back to
+ * back into dst; offsets[count+1] receives each bitmap's start, in values.  dst == NULL: the offsets only.
+ * offsets[count] > cap: RB_EINVAL, offsets still filled, nothing written.
+ * rb_stats: main kernel k_set_values, tasks = containers decoded, output_bytes = 4 * offsets[count],
+ * result_cardinality = offsets[count], input_bytes = payload + 16 B of each of those containers. */
+int rbgpu_set_values(const rbgpu_set *set, uint32_t first, uint32_t count, uint32_t *dst, uint64_t cap,
+                     uint64_t *offsets);
+/* The same into device memory d_dst (cap values); offsets on the host; synchronous like rbgpu_set_serialize_device.
+ * The offsets and the decode run in stream order with no host wait between them. */
+int rbgpu_set_values_device(const rbgpu_set *set, uint32_t first, uint32_t count, uint32_t *d_dst, uint64_t cap,
+                            uint64_t *offsets);
+/* n point queries, any order, duplicates allowed; query i goes to bitmap[i] of the set (bitmap == NULL: bitmap 0
+ * for all).  rb_stats: kernel k_set_contains / k_set_rank / k_set_select, tasks = n.
+ * RoaringBitmap.contains(int) (:1693): out[i] = 1 when values[i] is a member, else 0. */
+int rbgpu_set_contains(const rbgpu_set *set, const uint32_t *bitmap, const uint32_t *values, uint64_t n,
+                       uint8_t *out);
+/* RoaringBitmap.rankLong (:2574; rank, :2622, is its int cast): out[i] = the number of members <= values[i],
+ * compared as unsigned — 0 below the first member, the cardinality from the last one on.
+ * rangeCardinality(start, end) (:2590) is rank(end - 1) - rank(start - 1): two queries of one call. */
+int rbgpu_set_rank(const rbgpu_set *set, const uint32_t *bitmap, const uint32_t *values, uint64_t n, uint64_t *out);
+/* RoaringBitmap.select(int j) (:2820): out[i] = the j[i]-th smallest member, counting from 0, and found[i] = 1;
+ * j[i] >= the cardinality: out[i] = 0, found[i] = 0 and the call still returns RB_OK (the reference throws
+ * IllegalArgumentException per call; a batch reports per query).  first() / last() (:2972, :2977) are
+ * select(0) / select(cardinality - 1). */
+int rbgpu_set_select(const rbgpu_set *set, const uint32_t *bitmap, const uint64_t *j, uint64_t n, uint32_t *out,
+                     uint8_t *found);
+
 /* ---- pairwise set algebra (static RoaringBitmap ops) ------------------------------- */
 /* An a_idx / b_idx entry equal to RB_EMPTY_BITMAP stands for an empty bitmap (no containers): op with
  * it clones the other side's containers (or, xor, andNot with an empty right side) or gives nothing. */

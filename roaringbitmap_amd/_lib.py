@@ -115,6 +115,12 @@ SIGNATURES = {
     "rbgpu_set_serialize": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _U64P]),
     "rbgpu_set_serialize_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _U64P]),
     "rbgpu_set_download": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(RbSoa)]),
+    # the value read-out: destination, query and output arrays as void* (plain addresses, host or device)
+    "rbgpu_set_values": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _U64P]),
+    "rbgpu_set_values_device": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, _U64P]),
+    "rbgpu_set_contains": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rbgpu_set_rank": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rbgpu_set_select": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     # index arrays as void* (engine passes plain addresses: see engine._idx_addr)
     "rbgpu_pairwise": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_uint32, C.POINTER(_P)]),
     "rbgpu_pairwise_cardinality": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_uint32, _U64P]),

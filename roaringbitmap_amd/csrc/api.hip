@@ -70,6 +70,7 @@ void set_release(rbgpu_set *s) {
   p.release(s->krec);
   p.release(s->bsi_table);
   p.release(s->bsi_klist);
+  p.release(s->cpre);
   rbgpu_ctx *ctx = s->ctx;
   s->ctx = nullptr;
   ctx_unref(ctx);
@@ -614,7 +615,7 @@ int rbgpu_open(int device, rbgpu_ctx **out) {
   // the first launch of one of its kernels (~1 ms each), which otherwise lands in that call's time and in a
   // set's first-use setup (rbgpu_set_setup_parts)
   for (auto w : {warm_pairwise, warm_scan, warm_wide, warm_wide_runs, warm_wide_xor, warm_bsi, warm_codec, warm_setops,
-                 warm_generate})
+                 warm_generate, warm_values})
     w(c->stream);
   if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
     rbgpu_close(c);
@@ -1032,6 +1033,56 @@ int rbgpu_set_serialize_device(const rbgpu_set *s, uint32_t first, uint32_t coun
   int rc = check_ctx(s->ctx);
   if (rc) return rc;
   return serialize_device(s, first, count, d_dst, cap, offsets, false);
+}
+
+// ---------------------------------------------------------------- value read-out (values.hip)
+static int set_values_call(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *dst, uint64_t cap,
+                           uint64_t *offsets, bool host_dst) {
+  SETTLE(s);
+  if (!s || !offsets) return fail(RB_EINVAL, "null argument");
+  if ((uint64_t)first + count > s->nb) return fail(RB_EINVAL, "bitmap range out of bounds");
+  const int rc = check_ctx(s->ctx);
+  if (rc) return rc;
+  return set_values(s, first, count, dst, cap, offsets, host_dst);
+}
+
+int rbgpu_set_values(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *dst, uint64_t cap,
+                     uint64_t *offsets) {
+  return set_values_call(s, first, count, dst, cap, offsets, true);
+}
+
+int rbgpu_set_values_device(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *d_dst, uint64_t cap,
+                            uint64_t *offsets) {
+  return set_values_call(s, first, count, d_dst, cap, offsets, false);
+}
+
+// the batched lookups' arguments: every bitmap[i] names a bitmap of the set (checked here, before any launch)
+static int set_lookup_call(const rbgpu_set *s, int kind, const uint32_t *bitmap, const void *queries, uint64_t n,
+                           void *out, uint8_t *found) {
+  SETTLE(s);
+  if (!s) return fail(RB_EINVAL, "null set");
+  if (n && (!queries || !out || (kind == kLookupSelect && !found))) return fail(RB_EINVAL, "null argument");
+  if (n && !bitmap && !s->nb) return fail(RB_EINVAL, "the set holds no bitmap 0");
+  if (bitmap)
+    for (uint64_t i = 0; i < n; ++i)
+      if (bitmap[i] >= s->nb)
+        return fail(RB_EINVAL, "bitmap[%llu] = %u: the set holds %u bitmaps", (unsigned long long)i, bitmap[i], s->nb);
+  const int rc = check_ctx(s->ctx);
+  if (rc) return rc;
+  return set_lookup(s, kind, bitmap, queries, n, out, found);
+}
+
+int rbgpu_set_contains(const rbgpu_set *s, const uint32_t *bitmap, const uint32_t *values, uint64_t n, uint8_t *out) {
+  return set_lookup_call(s, kLookupContains, bitmap, values, n, out, nullptr);
+}
+
+int rbgpu_set_rank(const rbgpu_set *s, const uint32_t *bitmap, const uint32_t *values, uint64_t n, uint64_t *out) {
+  return set_lookup_call(s, kLookupRank, bitmap, values, n, out, nullptr);
+}
+
+int rbgpu_set_select(const rbgpu_set *s, const uint32_t *bitmap, const uint64_t *j, uint64_t n, uint32_t *out,
+                     uint8_t *found) {
+  return set_lookup_call(s, kLookupSelect, bitmap, j, n, out, found);
 }
 
 // ---------------------------------------------------------------- pairwise

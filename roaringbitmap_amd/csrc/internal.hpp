@@ -239,6 +239,9 @@ struct rbgpu_set {
   int32_t *bsi_table = nullptr;
   uint32_t *bsi_klist = nullptr;
   uint32_t bsi_nk = 0, bsi_kmin = 0, bsi_kmax = 0; // ebM's key count and first / last key
+  // the value read-out (values.hip): cpre[c] = members in the set's containers before c, u64[nc + 1] (the exclusive
+  // prefix of `card` in set order, so a bitmap's members start at cpre[begin[b]]), built on first use
+  uint64_t *cpre = nullptr;
   rbg::SetView view() const { return rbg::SetView{begin, key, type, card, nruns, off, payload}; }
 };
 
@@ -281,7 +284,7 @@ struct DeriveTimer {
     if (e0 && e1 && hipEventRecord(e1, s->ctx->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess &&
         hipEventElapsedTime(&ms, e0, e1) == hipSuccess) {
       s->derive_ms += ms;
-      s->part_ms[part] += ms;
+      if (part >= 0) s->part_ms[part] += ms; // -1: an item rbgpu_set_setup_parts does not list (the total only)
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
@@ -339,6 +342,14 @@ int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uin
                uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count, bool host_dst);
 int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n, uint64_t *values,
                    uint8_t *exists);
+// values.hip, the read-out of plain sets: the members of bitmaps [first, first + count) back to back (host_dst:
+// dst is host memory, else device memory; null: the offsets only), and batched contains / rank / select (host
+// arrays; `bitmap` may be null: bitmap 0)
+int set_values(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *dst, uint64_t cap, uint64_t *offsets,
+               bool host_dst);
+enum { kLookupContains = 0, kLookupRank = 1, kLookupSelect = 2 };
+int set_lookup(const rbgpu_set *s, int kind, const uint32_t *bitmap, const void *queries, uint64_t n, void *out,
+               uint8_t *found);
 // api.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
 int set_key_subset(const rbgpu_set *s, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
 int set_gather(const rbgpu_set *s, const uint32_t *idx, uint32_t n, rbgpu_set **out);

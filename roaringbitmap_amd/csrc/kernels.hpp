@@ -25,6 +25,7 @@ void warm_generate(hipStream_t st);
 void warm_pairwise(hipStream_t st);
 void warm_scan(hipStream_t st);
 void warm_setops(hipStream_t st);
+void warm_values(hipStream_t st);
 void warm_wide(hipStream_t st);
 void warm_wide_runs(hipStream_t st);
 void warm_wide_xor(hipStream_t st);

@@ -284,6 +284,67 @@ class DeviceSet:
                                                     offs.ctypes.data_as(L._U64P)))
         return offs
 
+    # ---- the value read-out: the members themselves, decoded on the device (values.hip)
+    def _value_offsets(self, first: int, count: int) -> np.ndarray:
+        offs = np.zeros(count + 1, np.uint64)
+        L.check(L.lib().rbgpu_set_values(self.h, first, count, None, 0, offs.ctypes.data_as(L._U64P)))
+        return offs
+
+    def to_arrays(self, first: int = 0, count: Optional[int] = None) -> List[np.ndarray]:
+        """RoaringBitmap.toArray of bitmaps [first, first+count): one ascending uint32 array each
+        (rbgpu_set_values: an offsets-only call sizes the buffer, a second call fills it)."""
+        count = len(self) - first if count is None else count
+        offs = self._value_offsets(first, count)
+        vals = np.zeros(int(offs[count]), np.uint32)
+        if len(vals):
+            L.check(L.lib().rbgpu_set_values(self.h, first, count, vals.ctypes.data, len(vals),
+                                             offs.ctypes.data_as(L._U64P)))
+        return [vals[int(offs[i]):int(offs[i + 1])] for i in range(count)]
+
+    def values_device(self, dst_ptr: int, cap: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The same values written by the GPU into device memory at dst_ptr (uint32[cap]), back to back
+        (rbgpu_set_values_device); returns the count+1 offsets, in values.  dst_ptr = 0: the offsets only; a
+        total above cap raises InvalidArgument and writes nothing."""
+        count = len(self) - first if count is None else count
+        offs = np.zeros(count + 1, np.uint64)
+        L.check(L.lib().rbgpu_set_values_device(self.h, first, count, C.c_void_p(dst_ptr or None), int(cap),
+                                                offs.ctypes.data_as(L._U64P)))
+        return offs
+
+    @staticmethod
+    def _queries(q, dtype, bitmap):
+        q = np.ascontiguousarray(np.asarray(q, dtype=dtype).ravel())
+        b = None if bitmap is None else np.ascontiguousarray(np.asarray(bitmap, dtype=np.uint32).ravel())
+        if b is not None and len(b) != len(q):
+            raise ValueError("bitmap and the queries differ in length")
+        return q, b, (b.ctypes.data if b is not None and len(b) else None)
+
+    def contains(self, values, bitmap=None) -> np.ndarray:
+        """RoaringBitmap.contains for a batch (any order, duplicates allowed): bool[n]; query i goes to bitmap
+        bitmap[i] of the set (None: bitmap 0) (rbgpu_set_contains)."""
+        v, b, bp = self._queries(values, np.uint32, bitmap)
+        out = np.zeros(len(v), np.uint8)
+        L.check(L.lib().rbgpu_set_contains(self.h, bp, v.ctypes.data if len(v) else None, len(v),
+                                           out.ctypes.data if len(v) else None))
+        return out.astype(bool)
+
+    def rank(self, values, bitmap=None) -> np.ndarray:
+        """RoaringBitmap.rankLong for a batch: uint64[n], the members <= values[i] (rbgpu_set_rank)."""
+        v, b, bp = self._queries(values, np.uint32, bitmap)
+        out = np.zeros(len(v), np.uint64)
+        L.check(L.lib().rbgpu_set_rank(self.h, bp, v.ctypes.data if len(v) else None, len(v),
+                                       out.ctypes.data if len(v) else None))
+        return out
+
+    def select(self, j, bitmap=None) -> Tuple[np.ndarray, np.ndarray]:
+        """RoaringBitmap.select for a batch: (values uint32, found bool); j[i] at or past the cardinality gives
+        (0, False) (rbgpu_set_select)."""
+        q, b, bp = self._queries(j, np.uint64, bitmap)
+        out, found = np.zeros(len(q), np.uint32), np.zeros(len(q), np.uint8)
+        L.check(L.lib().rbgpu_set_select(self.h, bp, q.ctypes.data if len(q) else None, len(q),
+                                         out.ctypes.data if len(q) else None, found.ctypes.data if len(q) else None))
+        return out, found.astype(bool)
+
     def device_view(self) -> dict:
         """rbgpu_set_device_view: device addresses of the SoA (never blocks; n_containers is None while an
         asynchronous result is pending)."""

@@ -86,7 +86,65 @@ class RoaringBitmap:
         return self._set.n_containers == 0
 
     def toArray(self) -> np.ndarray:
-        return self._set.download().values(0)
+        """RoaringBitmap.toArray (RoaringBitmap.java:3224): decoded on the device (rbgpu_set_values)."""
+        return self._set.to_arrays()[0]
+
+    # ---- the value side: contains / rank / select (RoaringBitmap.java:1693, 2574, 2622, 2820), on the device
+    def contains(self, x):
+        """contains(int x); an array of values gives an array of bools (one batched call)."""
+        if np.ndim(x) == 0:
+            return bool(self._set.contains([int(x) & 0xFFFFFFFF])[0])
+        return self._set.contains(np.asarray(x).astype(np.uint32))
+
+    def rankLong(self, x):
+        """rankLong(int x): the members <= x, compared as unsigned; an array gives an array."""
+        if np.ndim(x) == 0:
+            return int(self._set.rank([int(x) & 0xFFFFFFFF])[0])
+        return self._set.rank(np.asarray(x).astype(np.uint32))
+
+    def rank(self, x):
+        """rank(int x) = (int) rankLong(x)."""
+        return self.rankLong(x)
+
+    def select(self, j):
+        """select(int j): the j-th smallest member, from 0.  ValueError where the reference throws
+        IllegalArgumentException (j at or past the cardinality); an array raises when any index is."""
+        scalar = np.ndim(j) == 0
+        q = np.asarray([int(j) & 0xFFFFFFFF] if scalar else j, dtype=np.uint64)
+        vals, found = self._set.select(q)
+        if not found.all():
+            bad = int(q[np.argmin(found)])
+            raise ValueError(f"You are trying to select the {bad}th value when the cardinality is "
+                             f"{self.getCardinality()}.")
+        return int(vals[0]) if scalar else vals
+
+    def first(self) -> int:
+        """first() (:2972): ValueError on an empty bitmap (the reference's NoSuchElementException)."""
+        vals, found = self._set.select([0])
+        if not found[0]:
+            raise ValueError("Empty RoaringBitmap")
+        return int(vals[0])
+
+    def last(self) -> int:
+        """last() (:2977): ValueError on an empty bitmap (the reference's NoSuchElementException)."""
+        card = self.getCardinality()
+        if card == 0:
+            raise ValueError("Empty RoaringBitmap")
+        return int(self._set.select([card - 1])[0][0])
+
+    def rangeCardinality(self, start: int, end: int) -> int:
+        """rangeCardinality(long start, long end) (:2590): the members in [start, end), both compared as unsigned
+        longs (values past 2^32 hold no member) — rank(end - 1) - rank(start - 1) as two queries of one call."""
+        start, end = int(start) & (2**64 - 1), int(end) & (2**64 - 1)
+        if start >= end:
+            return 0
+        start, end = min(start, 2**32), min(end, 2**32)
+        if start >= end:
+            return 0
+        if start == 0:
+            return int(self._set.rank([end - 1])[0])
+        r = self._set.rank([end - 1, start - 1])
+        return int(r[0]) - int(r[1])
 
     def runOptimize(self) -> bool:
         """RoaringBitmap.runOptimize (RoaringBitmap.java:2764-2775) on the device: each container takes
