@@ -242,6 +242,44 @@ int rbgpu_set_rank(const rbgpu_set *set, const uint32_t *bitmap, const uint32_t 
 int rbgpu_set_select(const rbgpu_set *set, const uint32_t *bitmap, const uint64_t *j, uint64_t n, uint32_t *out,
                      uint8_t *found);
 
+/* ---- building from values (the inverse of rbgpu_set_values* and rbgpu_bsi_values*) -----
+ * Member values in, canonical containers out, on the device: the values are grouped by (bitmap, high key), each
+ * group is OR-ed into a 65536-bit image by one wave, and the image is classified and written like every other
+ * result (build.hip).  The returned sets are ordinary immutable sets; their payload arena is tight (the sum of the
+ * payloads, each rounded up to 16 B).  Bad arguments — offsets that descend, a null array with elements to read, a
+ * null out, an unknown flag bit — give RB_EINVAL before any launch.
+ * rb_stats: main kernel k_set_build, tasks = containers built = result_containers, result_cardinality = members
+ * of the result, output_bytes = payload + 16 B per container, input_bytes = 4 B per value / 12 B per pair. */
+enum rb_build_flags { RB_BUILD_RUN_OPTIMIZE = 1 };
+/* Elements per block of the container-discovery pass (a bitmap start or a key change may fall on any residue). */
+#define RB_BUILD_TILE 1024
+/* RoaringBitmap.bitmapOf / add(int...) / addN (RoaringBitmap.java:483-566) for n bitmaps: bitmap i holds
+ * values[offsets[i], offsets[i+1]), in any order, duplicates allowed; offsets[n+1] on the host.  Without a flag
+ * the containers are bitmapOf's: an Array up to 4096 members, a Bitmap above, never a Run.  With
+ * RB_BUILD_RUN_OPTIMIZE they are those of bitmapOf(...) followed by runOptimize() (RoaringBitmap.java:2764-2775;
+ * ArrayContainer.java:1085-1099, BitmapContainer.java:1227-1246).  For input whose high keys ascend that is also
+ * what a RoaringBitmapWriter with runCompress appends (ContainerAppender.java:130-137); a writer fed descending
+ * high keys is path-dependent in the reference (it flushes a container whenever the key changes and merges it
+ * into what is there, so the types depend on the order of arrival) and is NOT reproduced: the result here depends
+ * on the set of values only.  An empty bitmap gives no containers; n == 0 gives an empty set. */
+int rbgpu_set_from_values(rbgpu_ctx *ctx, const uint32_t *values, const uint64_t *offsets, uint32_t n,
+                          uint32_t flags, rbgpu_set **out);
+/* The same for values in device memory (offsets on the host).  d_values is only read.  Synchronous like
+ * rbgpu_set_from_serialized_device. */
+int rbgpu_set_from_values_device(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *offsets, uint32_t n,
+                                 uint32_t flags, rbgpu_set **out);
+/* Roaring64BitmapSliceIndex.setValues on a fresh index (bsi/.../longlong/Roaring64BitmapSliceIndex.java:291-348):
+ * n (column, value) pairs in any order; a column given more than once keeps its last value (setValueInternal's
+ * add / remove per slice).  Values are unsigned 64-bit.  The result set is the slices bA[0..nbits) and then ebM
+ * (the layout of rbgpu_generate_bsi), nbits = max(1, bit length of the largest value); *min_value / *max_value
+ * (either may be NULL) receive the smallest / largest value kept.  n == 0: a one-bitmap set (an empty ebM),
+ * min = max = 0.  flags as above (Roaring64BitmapSliceIndex.runOptimize, :155-162). */
+int rbgpu_bsi_from_pairs(rbgpu_ctx *ctx, const uint32_t *cols, const uint64_t *vals, uint64_t n, uint32_t flags,
+                         rbgpu_set **out, uint64_t *min_value, uint64_t *max_value);
+/* The same for pairs in device memory (only read); synchronous. */
+int rbgpu_bsi_from_pairs_device(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_vals, uint64_t n,
+                                uint32_t flags, rbgpu_set **out, uint64_t *min_value, uint64_t *max_value);
+
 /* ---- pairwise set algebra (static RoaringBitmap ops) ------------------------------- */
 /* An a_idx / b_idx entry equal to RB_EMPTY_BITMAP stands for an empty bitmap (no containers): op with
  * it clones the other side's containers (or, xor, andNot with an empty right side) or gives nothing. */

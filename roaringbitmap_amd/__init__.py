@@ -10,7 +10,7 @@ from ._lib import (AND, ANDNOT, ARRAY, BITMAP, FAST_AND, FAST_OR, FAST_XOR, NAIV
                    WORKSHY_AND, XOR, FormatError, InvalidArgument, RbError)
 from .engine import Context, DeviceSet, HostSoA, default_context, soa_from_values
 from .roaring import (BufferFastAggregation, BufferParallelAggregation, FastAggregation, ParallelAggregation, Roaring64Bitmap,
-                      Roaring64NavigableMap, RoaringBitmap)
+                      Roaring64NavigableMap, RoaringBitmap, RoaringBitmapWriter)
 from .bsi import Operation, Roaring64BitmapSliceIndex, RoaringBitmapSliceIndex
 from ._lib import BSI_EQ, BSI_GE, BSI_GT, BSI_LE, BSI_LT, BSI_NEQ, BSI_RANGE
 from ._lib import HORIZONTAL_OR, HORIZONTAL_XOR, PQ_OR, PQ_XOR
@@ -25,7 +25,7 @@ __all__ = [
     "BUFFER_NAIVE_OR", "BUFFER_PQ_OR", "BUFFER_PQ_OR_ITER", "BUFFER_PQ_XOR", "BufferFastAggregation", "BufferParallelAggregation",
     "WL_FILTER_POSTING", "WL_WIDE_DENSE", "WL_WIDE_MIXED", "WL_WIDE_RUNS",
     "Context", "DeviceSet", "HostSoA", "default_context", "soa_from_values",
-    "RoaringBitmap", "FastAggregation", "ParallelAggregation", "Roaring64Bitmap", "Roaring64NavigableMap",
+    "RoaringBitmap", "RoaringBitmapWriter", "FastAggregation", "ParallelAggregation", "Roaring64Bitmap", "Roaring64NavigableMap",
     "DeviceSet64", "RB64_BITMAP", "RB64_NAVIGABLE",
     "Roaring64BitmapSliceIndex", "RoaringBitmapSliceIndex", "Operation",
     "BSI_EQ", "BSI_NEQ", "BSI_LE", "BSI_LT", "BSI_GE", "BSI_GT", "BSI_RANGE",

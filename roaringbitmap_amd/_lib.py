@@ -24,6 +24,8 @@ RB64_BITMAP, RB64_NAVIGABLE = 0, 1  # rbgpu.h rb64_flavor: Roaring64Bitmap / Roa
 EMPTY_BITMAP = 0xFFFFFFFF           # RB_EMPTY_BITMAP pair index
 WL_FILTER_POSTING, WL_WIDE_DENSE, WL_WIDE_MIXED, WL_WIDE_RUNS = range(4)
 BSI_EQ, BSI_NEQ, BSI_LE, BSI_LT, BSI_GE, BSI_GT, BSI_RANGE = range(7)  # BitmapSliceIndex.Operation
+BUILD_RUN_OPTIMIZE = 1  # rb_build_flags
+BUILD_TILE = 1024       # RB_BUILD_TILE: elements per block of the value build's container discovery
 
 
 class RbSoa(C.Structure):
@@ -121,6 +123,13 @@ SIGNATURES = {
     "rbgpu_set_contains": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rbgpu_set_rank": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rbgpu_set_select": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    # building from values: value / column / value arrays as void* (host or device addresses)
+    "rbgpu_set_from_values": (C.c_int, [_P, C.c_void_p, _U64P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "rbgpu_set_from_values_device": (C.c_int, [_P, C.c_void_p, _U64P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),
+    "rbgpu_bsi_from_pairs": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_P), _U64P,
+                                       _U64P]),
+    "rbgpu_bsi_from_pairs_device": (C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(_P),
+                                              _U64P, _U64P]),
     # index arrays as void* (engine passes plain addresses: see engine._idx_addr)
     "rbgpu_pairwise": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_uint32, C.POINTER(_P)]),
     "rbgpu_pairwise_cardinality": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_uint32, _U64P]),

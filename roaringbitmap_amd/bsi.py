@@ -62,6 +62,14 @@ class Roaring64BitmapSliceIndex:
         b._cols = None
         return b
 
+    @classmethod
+    def from_pairs(cls, cols, vals, run_optimize: bool = False) -> "Roaring64BitmapSliceIndex":
+        """setValues(pairs) on a fresh index (Roaring64BitmapSliceIndex.java:291-348), then runOptimize when asked,
+        built on the device from the two arrays (rbgpu_bsi_from_pairs): any order, the last value of a column
+        kept, values unsigned 64-bit."""
+        dset, lo, hi = default_context().bsi_build(cols, vals, run_optimize)
+        return cls.from_device(dset, lo, hi)
+
     def runOptimize(self) -> None:
         self._run_optimized = True
         self._dev = None

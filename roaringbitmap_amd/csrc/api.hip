@@ -615,7 +615,7 @@ int rbgpu_open(int device, rbgpu_ctx **out) {
   // the first launch of one of its kernels (~1 ms each), which otherwise lands in that call's time and in a
   // set's first-use setup (rbgpu_set_setup_parts)
   for (auto w : {warm_pairwise, warm_scan, warm_wide, warm_wide_runs, warm_wide_xor, warm_bsi, warm_codec, warm_setops,
-                 warm_generate, warm_values})
+                 warm_generate, warm_values, warm_build})
     w(c->stream);
   if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
     rbgpu_close(c);
@@ -1083,6 +1083,79 @@ int rbgpu_set_rank(const rbgpu_set *s, const uint32_t *bitmap, const uint32_t *v
 int rbgpu_set_select(const rbgpu_set *s, const uint32_t *bitmap, const uint64_t *j, uint64_t n, uint32_t *out,
                      uint8_t *found) {
   return set_lookup_call(s, kLookupSelect, bitmap, j, n, out, found);
+}
+
+// ---------------------------------------------------------------- building from values (build.hip)
+static int set_from_values_call(rbgpu_ctx *ctx, const uint32_t *values, const uint64_t *offsets, uint32_t n,
+                                uint32_t flags, rbgpu_set **out, bool host_src) {
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!out) return fail(RB_EINVAL, "null out");
+  *out = nullptr;
+  if (flags & ~(uint32_t)RB_BUILD_RUN_OPTIMIZE) return fail(RB_EINVAL, "unknown build flags 0x%x", flags);
+  if (n && !offsets) return fail(RB_EINVAL, "null offsets");
+  for (uint32_t i = 0; i < n; ++i)
+    if (offsets[i + 1] < offsets[i]) return fail(RB_EINVAL, "offsets not monotone at %u", i);
+  const uint64_t base = n ? offsets[0] : 0, total = n ? offsets[n] - base : 0;
+  if (total && !values) return fail(RB_EINVAL, "null values");
+  if (!host_src || !total) return build_set_values(ctx, values, offsets, n, flags, out);
+  uint32_t *d_values = nullptr;
+  if (ctx->pool.alloc((void **)&d_values, total * 4)) return fail(RB_ENOMEM, "staging of %llu values", (unsigned long long)total);
+  std::vector<uint64_t> rel((size_t)n + 1);
+  for (uint32_t i = 0; i <= n; ++i) rel[i] = offsets[i] - base;
+  if (hipMemcpyAsync(d_values, values + base, total * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+    ctx->pool.release(d_values);
+    return fail(RB_EDEVICE, "host-to-device copy failed");
+  }
+  rc = build_set_values(ctx, d_values, rel.data(), n, flags, out);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->pool.release(d_values);
+  return rc;
+}
+
+int rbgpu_set_from_values(rbgpu_ctx *ctx, const uint32_t *values, const uint64_t *offsets, uint32_t n, uint32_t flags,
+                          rbgpu_set **out) {
+  return set_from_values_call(ctx, values, offsets, n, flags, out, true);
+}
+
+int rbgpu_set_from_values_device(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *offsets, uint32_t n,
+                                 uint32_t flags, rbgpu_set **out) {
+  return set_from_values_call(ctx, d_values, offsets, n, flags, out, false);
+}
+
+static int bsi_from_pairs_call(rbgpu_ctx *ctx, const uint32_t *cols, const uint64_t *vals, uint64_t n, uint32_t flags,
+                               rbgpu_set **out, uint64_t *min_value, uint64_t *max_value, bool host_src) {
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!out) return fail(RB_EINVAL, "null out");
+  *out = nullptr;
+  if (flags & ~(uint32_t)RB_BUILD_RUN_OPTIMIZE) return fail(RB_EINVAL, "unknown build flags 0x%x", flags);
+  if (n && (!cols || !vals)) return fail(RB_EINVAL, "null pairs");
+  if (!host_src || !n) return build_bsi_pairs(ctx, cols, vals, n, flags, out, min_value, max_value);
+  uint32_t *d_cols = nullptr;
+  uint64_t *d_vals = nullptr;
+  if (ctx->pool.alloc((void **)&d_cols, n * 4) || ctx->pool.alloc((void **)&d_vals, n * 8)) {
+    ctx->pool.release(d_cols);
+    return fail(RB_ENOMEM, "staging of %llu pairs", (unsigned long long)n);
+  }
+  if (hipMemcpyAsync(d_cols, cols, n * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipMemcpyAsync(d_vals, vals, n * 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    rc = fail(RB_EDEVICE, "host-to-device copy failed");
+  else rc = build_bsi_pairs(ctx, d_cols, d_vals, n, flags, out, min_value, max_value);
+  (void)hipStreamSynchronize(ctx->stream);
+  ctx->pool.release(d_cols);
+  ctx->pool.release(d_vals);
+  return rc;
+}
+
+int rbgpu_bsi_from_pairs(rbgpu_ctx *ctx, const uint32_t *cols, const uint64_t *vals, uint64_t n, uint32_t flags,
+                         rbgpu_set **out, uint64_t *min_value, uint64_t *max_value) {
+  return bsi_from_pairs_call(ctx, cols, vals, n, flags, out, min_value, max_value, true);
+}
+
+int rbgpu_bsi_from_pairs_device(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_vals, uint64_t n,
+                                uint32_t flags, rbgpu_set **out, uint64_t *min_value, uint64_t *max_value) {
+  return bsi_from_pairs_call(ctx, d_cols, d_vals, n, flags, out, min_value, max_value, false);
 }
 
 // ---------------------------------------------------------------- pairwise

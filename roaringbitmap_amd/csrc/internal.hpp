@@ -350,6 +350,13 @@ int set_values(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *dst
 enum { kLookupContains = 0, kLookupRank = 1, kLookupSelect = 2 };
 int set_lookup(const rbgpu_set *s, int kind, const uint32_t *bitmap, const void *queries, uint64_t n, void *out,
                uint8_t *found);
+// build.hip, the inverse of the read-outs: a set from member values in device memory (bitmap i at
+// d_values[offsets[i], offsets[i + 1]), host offsets), and a BSI (slices, then ebM) from (column, value) pairs in
+// device memory; flags: rb_build_flags.  The inputs are only read.
+int build_set_values(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *offsets, uint32_t nb, uint32_t flags,
+                     rbgpu_set **out);
+int build_bsi_pairs(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_vals, uint64_t n, uint32_t flags,
+                    rbgpu_set **out, uint64_t *min_value, uint64_t *max_value);
 // api.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
 int set_key_subset(const rbgpu_set *s, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
 int set_gather(const rbgpu_set *s, const uint32_t *idx, uint32_t n, rbgpu_set **out);

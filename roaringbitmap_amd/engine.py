@@ -482,6 +482,53 @@ class Context:
     def upload_values(self, bitmaps: Sequence[np.ndarray], run_optimize: bool = False) -> DeviceSet:
         return self.upload_soa(soa_from_values(bitmaps, run_optimize))
 
+    # ---- building from values on the device (build.hip); upload_values above builds on the host
+    def _build_values(self, fn, ptr, offsets, run_optimize: bool) -> DeviceSet:
+        offs = np.ascontiguousarray(offsets, np.uint64).ravel()
+        if len(offs) == 0:
+            offs = np.zeros(1, np.uint64)
+        out = C.c_void_p()
+        L.check(fn(self.h, C.c_void_p(ptr or None), offs.ctypes.data_as(L._U64P), len(offs) - 1,
+                   L.BUILD_RUN_OPTIMIZE if run_optimize else 0, C.byref(out)))
+        return DeviceSet(self, out.value)
+
+    def build_values(self, bitmaps: Sequence[np.ndarray], run_optimize: bool = False) -> DeviceSet:
+        """RoaringBitmap.bitmapOf of each value list (any order, duplicates allowed), then runOptimize when asked:
+        the values go to the device as they are and the containers are built there (rbgpu_set_from_values)."""
+        arrs = [np.ascontiguousarray(np.asarray(b, dtype=np.uint32).ravel()) for b in bitmaps]
+        offs = np.zeros(len(arrs) + 1, np.uint64)
+        if arrs:
+            offs[1:] = np.cumsum([len(a) for a in arrs], dtype=np.uint64)
+        vals = np.concatenate(arrs) if arrs else np.zeros(0, np.uint32)
+        return self._build_values(L.lib().rbgpu_set_from_values, vals.ctypes.data if len(vals) else 0, offs,
+                                  run_optimize)
+
+    def build_values_device(self, ptr: int, offsets, run_optimize: bool = False) -> DeviceSet:
+        """The same for uint32 values already in device memory at ptr, bitmap i at [offsets[i], offsets[i+1])
+        (rbgpu_set_from_values_device); the values are only read."""
+        return self._build_values(L.lib().rbgpu_set_from_values_device, int(ptr), offsets, run_optimize)
+
+    def _bsi_build(self, fn, cols_ptr, vals_ptr, n: int, run_optimize: bool) -> Tuple[DeviceSet, int, int]:
+        out, lo, hi = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        L.check(fn(self.h, C.c_void_p(cols_ptr or None), C.c_void_p(vals_ptr or None), int(n),
+                   L.BUILD_RUN_OPTIMIZE if run_optimize else 0, C.byref(out), C.byref(lo), C.byref(hi)))
+        return DeviceSet(self, out.value), int(lo.value), int(hi.value)
+
+    def bsi_build(self, cols, vals, run_optimize: bool = False) -> Tuple[DeviceSet, int, int]:
+        """Roaring64BitmapSliceIndex.setValues on a fresh index: (set of the slices then ebM, min, max) from
+        (column, value) pairs in any order, the last value of a column kept (rbgpu_bsi_from_pairs)."""
+        c = np.ascontiguousarray(np.asarray(cols, dtype=np.uint32).ravel())
+        v = np.ascontiguousarray(np.asarray(vals, dtype=np.uint64).ravel())
+        if len(c) != len(v):
+            raise ValueError("cols and vals differ in length")
+        return self._bsi_build(L.lib().rbgpu_bsi_from_pairs, c.ctypes.data if len(c) else 0,
+                               v.ctypes.data if len(c) else 0, len(c), run_optimize)
+
+    def bsi_build_device(self, cols_ptr: int, vals_ptr: int, n: int,
+                         run_optimize: bool = False) -> Tuple[DeviceSet, int, int]:
+        """The same for uint32 columns and uint64 values in device memory (rbgpu_bsi_from_pairs_device)."""
+        return self._bsi_build(L.lib().rbgpu_bsi_from_pairs_device, int(cols_ptr), int(vals_ptr), n, run_optimize)
+
     def generate_keys(self, workload: int, n: int, key_lo: int, key_hi: int, seed: int = 42) -> DeviceSet:
         """The [key_lo, key_hi) shard of a wide synthetic workload (rbgpu_generate_keys)."""
         a = C.c_void_p()

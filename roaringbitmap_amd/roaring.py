@@ -221,6 +221,57 @@ class RoaringBitmap:
         return RoaringBitmap._pair_card(L.ANDNOT, x1, x2)
 
 
+class RoaringBitmapWriter:
+    """RoaringBitmapWriter.writer().runCompress(bool).get(), then add / addMany / flush / reset / get
+    (RoaringBitmapWriter.java, ContainerAppender.java:130-137): the values are buffered on the host and the
+    containers are built on the device when the bitmap is asked for (Context.build_values).  get() returns the bitmap
+    of everything added since the last reset(), bitmapOf's containers, run-optimized when runCompress is set — what
+    the reference's appender gives for input whose high keys ascend.  Fed descending high keys the reference's result
+    depends on the order of arrival; here it depends on the set of values only."""
+
+    class Wizard:
+        def __init__(self):
+            self._run_compress = True  # RoaringBitmapWriter.Wizard's default
+
+        def runCompress(self, run_compress: bool) -> "RoaringBitmapWriter.Wizard":
+            self._run_compress = bool(run_compress)
+            return self
+
+        def get(self) -> "RoaringBitmapWriter":
+            return RoaringBitmapWriter(self._run_compress)
+
+    @staticmethod
+    def writer() -> "RoaringBitmapWriter.Wizard":
+        return RoaringBitmapWriter.Wizard()
+
+    def __init__(self, run_compress: bool = True):
+        self._run_compress = run_compress
+        self._chunks = []
+        self._pending = []
+
+    def add(self, value: int) -> None:
+        self._pending.append(int(value) & 0xFFFFFFFF)
+
+    def addMany(self, *values) -> None:
+        v = np.asarray(values[0] if len(values) == 1 and np.ndim(values[0]) else values, dtype=np.uint32).ravel()
+        self.flush()
+        self._chunks.append(v.copy())
+
+    def flush(self) -> None:
+        if self._pending:
+            self._chunks.append(np.array(self._pending, np.uint32))
+            self._pending = []
+
+    def reset(self) -> None:
+        self._chunks, self._pending = [], []
+
+    def get(self) -> RoaringBitmap:
+        self.flush()
+        vals = np.concatenate(self._chunks) if self._chunks else np.zeros(0, np.uint32)
+        self._chunks = [vals]
+        return RoaringBitmap(default_context().build_values([vals], run_optimize=self._run_compress))
+
+
 def _gather(bitmaps: Sequence[RoaringBitmap]):
     """One device set holding each distinct bitmap once, and the member list naming them in call order:
     a bitmap passed twice is the same object twice (naive_and skips its smallest member by identity,
