@@ -554,21 +554,16 @@ __global__ __launch_bounds__(128, 2) void k_bsi_range(SetView bsi, SetView fnd, 
 // ---------------------------------------------------------------- host side
 static unsigned nblk(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
-// Keyed slots of one reduction: an 8 KiB payload slot per active key plus its type / card / runs.
+// Keyed slots of one reduction: an 8 KiB payload slot per active key plus its type / card / runs (the call's
+// scratch).
 struct KeyedSlots {
   uint8_t *payload = nullptr;
   WideOut wo{nullptr, nullptr, nullptr};
-  int alloc(rbgpu_ctx *ctx, uint32_t nk, bool with_payload) {
-    const uint64_t nk1 = std::max<uint32_t>(nk, 1);
-    if ((with_payload && ctx->pool.alloc((void **)&payload, nk1 * kBitmapBytes)) ||
-        ctx->pool.alloc((void **)&wo.type, nk1) || ctx->pool.alloc((void **)&wo.card, nk1 * 4) ||
-        ctx->pool.alloc((void **)&wo.nruns, nk1 * 2))
+  int alloc(Scratch &w, uint32_t nk, bool with_payload) {
+    if ((with_payload && !w.get(payload, (uint64_t)std::max<uint32_t>(nk, 1) * kBitmapBytes)) || !w.get(wo.type, nk) ||
+        !w.get(wo.card, nk) || !w.get(wo.nruns, nk))
       return fail(RB_ENOMEM, "bsi slots for %u keys", nk);
     return RB_OK;
-  }
-  void release(rbgpu_ctx *ctx, bool with_payload) {
-    if (with_payload) ctx->pool.release(payload);
-    for (void *p : {(void *)wo.type, (void *)wo.card, (void *)wo.nruns}) ctx->pool.release(p);
   }
 };
 
@@ -615,20 +610,16 @@ static int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *cs, uint32_t nbits
   int rc = ensure_h_begin(s);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
+  Scratch w(ctx->pool);
   int32_t *t = nullptr;
   uint32_t *kl = nullptr;
   uint64_t *bt = nullptr, *bts = nullptr;
-  if (ctx->pool.alloc((void **)&t, (nbits + 2ull) * 65536 * 4) || ctx->pool.alloc((void **)&kl, 65536 * 4ull) ||
-      ctx->pool.alloc((void **)&bt, 65537 * 8ull) || ctx->pool.alloc((void **)&bts, 65537 * 8ull)) {
-    for (void *p : {(void *)t, (void *)kl, (void *)bt, (void *)bts}) ctx->pool.release(p);
+  if (!w.get(t, (nbits + 2ull) * 65536) || !w.get(kl, 65536) || !w.get(bt, 65537) || !w.get(bts, 65537))
     return fail(RB_ENOMEM, "bsi tables");
-  }
   {
     DeriveTimer tm(s, 3);
-    if (hipMemsetAsync(t, 0xFF, (nbits + 1ull) * 65536 * 4, st) != hipSuccess) {
-      for (void *p : {(void *)t, (void *)kl, (void *)bt, (void *)bts}) ctx->pool.release(p);
+    if (hipMemsetAsync(t, 0xFF, (nbits + 1ull) * 65536 * 4, st) != hipSuccess)
       return fail(RB_EDEVICE, "bsi table memset failed");
-    }
     k_bsi_index<<<dim3(64, nbits + 1), 256, 0, st>>>(s->view(), 0, t);
     const int32_t *frow = t + (uint64_t)nbits * 65536;
     k_bsi_active<<<256, 256, 0, st>>>(frow, 0, 65536, bt);
@@ -637,28 +628,21 @@ static int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *cs, uint32_t nbits
     scan_blocks_multi(in1, out1, 1, 256, nullptr, st);
     k_bsi_list<<<256, 256, 0, st>>>(frow, 0, 65536, bts, kl);
   }
-  ctx->pool.release(bt); // stream-ordered: the pool hands them only to later work on this stream
-  ctx->pool.release(bts);
-  if (hipGetLastError() != hipSuccess) {
-    ctx->pool.release(t);
-    ctx->pool.release(kl);
-    return fail(RB_EDEVICE, "bsi table kernels failed");
-  }
+  w.give_back(bt); // stream-ordered: the pool hands them only to later work on this stream
+  w.give_back(bts);
+  if (hipGetLastError() != hipSuccess) return fail(RB_EDEVICE, "bsi table kernels failed");
   s->bsi_nk = (uint32_t)(s->h_begin[nbits + 1] - s->h_begin[nbits]);
   if (s->bsi_nk) { // ebM's first and last key: a key-range shard that holds them all takes the cached list
     uint32_t *h = reinterpret_cast<uint32_t *>(ctx->h_pinned);
     if (hipMemcpyAsync(h, kl, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(h + 1, kl + s->bsi_nk - 1, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      ctx->pool.release(t);
-      ctx->pool.release(kl);
+        hipStreamSynchronize(st) != hipSuccess)
       return fail(RB_EDEVICE, "bsi key list read-back failed");
-    }
     s->bsi_kmin = h[0];
     s->bsi_kmax = h[1];
   }
-  s->bsi_table = t;
-  s->bsi_klist = kl;
+  s->bsi_table = w.keep(t);
+  s->bsi_klist = w.keep(kl);
   // keys read, table entries written (4 B per container), ebM's key list written
   const uint64_t b = 6ull * (s->h_begin[nbits + 1] - s->h_begin[0]) + 4ull * s->bsi_nk;
   s->derive_bytes += b;
@@ -668,20 +652,14 @@ static int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *cs, uint32_t nbits
 
 // The tables of a call (ensure_bsi_tables, plus the foundSet's row) and F's keys inside [key_lo, key_hi), F = the
 // foundSet or ebM: ebM's over the whole key range are the set's cached list; a foundSet's or a shard's are
-// listed per call, and their count comes from F's host CSR over the whole range, else by a read-back.
+// listed per call (in the call's scratch), and their count comes from F's host CSR over the whole range, else by
+// a read-back.
 struct BsiKeys {
   const uint32_t *d_klist = nullptr;
   uint32_t nk = 0;
-  uint64_t *d_active = nullptr, *d_pos = nullptr;
-  uint32_t *d_kl = nullptr;
-  void release(rbgpu_ctx *ctx) {
-    for (void *p : {(void *)d_active, (void *)d_pos, (void *)d_kl}) ctx->pool.release(p);
-    d_active = d_pos = nullptr;
-    d_kl = nullptr;
-  }
 };
-static int bsi_keys(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint32_t nbits, const rbgpu_set *found, uint32_t key_lo,
-                    uint32_t key_hi, BsiKeys &ks) {
+static int bsi_keys(rbgpu_ctx *ctx, Scratch &w, const rbgpu_set *bsi, uint32_t nbits, const rbgpu_set *found,
+                    uint32_t key_lo, uint32_t key_hi, BsiKeys &ks) {
   hipStream_t st = ctx->stream;
   // key -> container tables: rows 0..nbits-1 slices, nbits ebM (the set's, cached), nbits+1 foundSet
   int rc = ensure_bsi_tables(ctx, bsi, nbits);
@@ -699,18 +677,16 @@ static int bsi_keys(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint32_t nbits, const 
     ks.nk = bsi->bsi_nk;
     return RB_OK;
   }
-  if (ctx->pool.alloc((void **)&ks.d_active, 65537 * 8ull) || ctx->pool.alloc((void **)&ks.d_pos, 65537 * 8ull) ||
-      ctx->pool.alloc((void **)&ks.d_kl, 65536 * 4ull)) {
-    ks.release(ctx);
-    return fail(RB_ENOMEM, "bsi key list");
-  }
+  uint64_t *d_active = nullptr, *d_pos = nullptr;
+  uint32_t *d_kl = nullptr;
+  if (!w.get(d_active, 65537) || !w.get(d_pos, 65537) || !w.get(d_kl, 65536)) return fail(RB_ENOMEM, "bsi key list");
   const int32_t *frow = d_table + (uint64_t)(found ? nbits + 1 : nbits) * 65536;
-  k_bsi_active<<<256, 256, 0, st>>>(frow, key_lo, key_hi, ks.d_active);
-  const uint64_t *in1[1] = {ks.d_active};
-  uint64_t *out1[1] = {ks.d_pos};
+  k_bsi_active<<<256, 256, 0, st>>>(frow, key_lo, key_hi, d_active);
+  const uint64_t *in1[1] = {d_active};
+  uint64_t *out1[1] = {d_pos};
   scan_blocks_multi(in1, out1, 1, 256, nullptr, st);
-  k_bsi_list<<<256, 256, 0, st>>>(frow, key_lo, key_hi, ks.d_pos, ks.d_kl);
-  ks.d_klist = ks.d_kl;
+  k_bsi_list<<<256, 256, 0, st>>>(frow, key_lo, key_hi, d_pos, d_kl);
+  ks.d_klist = d_kl;
   const rbgpu_set *fs = found ? found : bsi;
   const uint32_t fb = found ? 0u : nbits;
   hipError_t e = hipSuccess;
@@ -718,15 +694,12 @@ static int bsi_keys(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint32_t nbits, const 
     ks.nk = (uint32_t)(fs->h_begin[fb + 1] - fs->h_begin[fb]);
     e = hipGetLastError();
   } else {
-    e = hipMemcpyAsync(ctx->h_pinned, ks.d_pos + 256, 8, hipMemcpyDeviceToHost, st);
+    e = hipMemcpyAsync(ctx->h_pinned, d_pos + 256, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipGetLastError();
     ks.nk = (uint32_t)ctx->h_pinned[0];
   }
-  if (e != hipSuccess) {
-    ks.release(ctx);
-    return fail(RB_EDEVICE, "bsi key list failed: %s", hipGetErrorString(e));
-  }
+  if (e != hipSuccess) return fail(RB_EDEVICE, "bsi key list failed: %s", hipGetErrorString(e));
   return RB_OK;
 }
 
@@ -739,8 +712,9 @@ static int bsi_range_one_launch(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgp
   int rc = ensure_call_words(ctx);
   if (!rc) rc = seq_begin(ctx);
   if (rc) return rc;
+  Scratch scratch(ctx->pool);
   uint64_t *kmeta = nullptr;
-  if (ctx->pool.alloc((void **)&kmeta, 8ull * nk)) return fail(RB_ENOMEM, "bsi key results");
+  if (!scratch.get(kmeta, nk)) return fail(RB_ENOMEM, "bsi key results");
   const uint32_t nblocks = nblk(nk, 2);
   BsiTail tl{kmeta, ctx->d_small_ctr, OutView{res->key, res->type, res->card, res->nruns, res->off}, res->begin,
              reinterpret_cast<uint64_t *>(ctx->d_small), ++ctx->small_seq, nblocks};
@@ -749,7 +723,7 @@ static int bsi_range_one_launch(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgp
                                        nbits, start, end, d_klist, nk, res->payload, tl);
   HIPCHK(hipEventRecord(ctx->ev[2], st));
   HIPCHK(hipEventRecord(ctx->ev[5], st));
-  ctx->pool.release(kmeta); // stream-ordered: handed out again only to later work on this stream
+  scratch.give_back(kmeta); // stream-ordered: handed out again only to later work on this stream
   bool seen = false;
   rc = seq_end(ctx, tl.seq, true, "bsi range", &seen);
   if (rc) return rc;
@@ -775,21 +749,16 @@ static int bsi_range_one_launch(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgp
 
 // An empty one-bitmap result (new RoaringBitmap()); rb_stats describes it: no kernel ran, nothing counted.
 static int empty_result(rbgpu_ctx *ctx, rbgpu_set **out) {
-  rbgpu_set *e = new rbgpu_set;
-  const int rc = set_alloc(ctx, e, 1, 0, 16);
-  if (rc) {
-    delete e;
-    return rc;
-  }
+  SetPtr e;
+  const int rc = make_set(ctx, 1, 0, 16, e);
+  if (rc) return rc;
   const uint64_t hb[2] = {0, 0};
   if (hipMemcpyAsync(e->begin, hb, 16, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-    rbgpu_set_free(e);
+      hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)
     return fail(RB_EDEVICE, "empty result");
-  }
   e->h_begin = {0, 0};
   for (int i = 0; i < kStatWords; ++i) ctx->words[i] = 0;
-  *out = e;
+  *out = e.release();
   return stats_fill(ctx, 0, 0, nullptr, 0, false);
 }
 
@@ -802,11 +771,10 @@ int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, ui
   if (sc >= 0 && (key_lo > 0 || key_hi < 65536)) {
     // a key-range shard of the shortcut's answer: the whole-range answer, restricted
     rbgpu_set *whole = nullptr;
-    int rc = bsi_compare(ctx, bsi, op, start, end, vmin, vmax, found, 0, 65536, &whole);
+    const int rc = bsi_compare(ctx, bsi, op, start, end, vmin, vmax, found, 0, 65536, &whole);
     if (rc) return rc;
-    rc = set_key_subset(whole, key_lo, key_hi, out);
-    rbgpu_set_free(whole);
-    return rc;
+    const SetPtr owner(whole);
+    return set_key_subset(whole, key_lo, key_hi, out);
   }
   if (sc >= 0) {
     // all = foundSet == null ? ebM.clone() : and(ebM, foundSet); empty = new bitmap.  rb_stats describes this
@@ -832,51 +800,33 @@ int bsi_compare(rbgpu_ctx *ctx, const rbgpu_set *bsi, int op, uint64_t start, ui
     return rbgpu_pairwise(ctx, RB_AND, bsi, found, &ai, &bi, 1, out); // its own stats: the AND's answer
   }
   // key -> container tables and F's keys in the range
+  Scratch w(ctx->pool);
   BsiKeys ks;
-  int rc = bsi_keys(ctx, bsi, nbits, found, key_lo, key_hi, ks);
+  int rc = bsi_keys(ctx, w, bsi, nbits, found, key_lo, key_hi, ks);
   if (rc) return rc;
   const int32_t *d_table = bsi->bsi_table;
   const uint32_t *d_klist = ks.d_klist;
   const uint32_t nk = ks.nk;
-  auto release = [&]() { ks.release(ctx); };
   // result set: one 8 KiB slot per key of F, compacted at the end
-  rbgpu_set *res = new rbgpu_set;
-  rc = set_alloc(ctx, res, 1, nk, (uint64_t)std::max<uint32_t>(nk, 1) * kBitmapBytes);
-  if (rc) {
-    delete res;
-    release();
-    return rc;
-  }
+  SetPtr res;
+  if ((rc = make_set(ctx, 1, nk, (uint64_t)std::max<uint32_t>(nk, 1) * kBitmapBytes, res))) return rc;
   if (op == 6 && nk) { // RANGE: one launch (k_bsi_range's tail compacts and hands the results to the host)
-    rc = bsi_range_one_launch(ctx, bsi, found, d_table, nbits, start, end, d_klist, nk, res);
-    release();
-    if (rc) {
-      rbgpu_set_free(res);
-      return rc;
-    }
-    *out = res;
+    if ((rc = bsi_range_one_launch(ctx, bsi, found, d_table, nbits, start, end, d_klist, nk, res.get()))) return rc;
+    *out = res.release();
     return RB_OK;
   }
   KeyedSlots fin;
-  rc = fin.alloc(ctx, nk, false);
-  if (!rc) {
-    HIPCHK(hipEventRecord(ctx->ev[1], st));
-    if (op != 6) {
-      bsi_chain(ctx, bsi, nbits, op, start, found, d_table, d_klist, nk, res->payload, fin.wo);
-    }
-    HIPCHK(hipEventRecord(ctx->ev[2], st));
-    rc = compact_keyed(ctx, d_klist, nk, fin.wo, res);
-    const KernelSpan spans[1] = {{op == 6 ? "k_bsi_range" : "k_bsi_chain", 0, 1, op == 6 ? 2ull * nk : nk}};
-    if (!rc) rc = stats_end(ctx, nk, 0, spans, 1);
-    if (!rc) keyed_result_count(ctx, res);
+  if ((rc = fin.alloc(w, nk, false))) return rc;
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  if (op != 6) {
+    bsi_chain(ctx, bsi, nbits, op, start, found, d_table, d_klist, nk, res->payload, fin.wo);
   }
-  fin.release(ctx, false);
-  release();
-  if (rc) {
-    rbgpu_set_free(res);
-    return rc;
-  }
-  *out = res;
+  HIPCHK(hipEventRecord(ctx->ev[2], st));
+  if ((rc = compact_keyed(ctx, d_klist, nk, fin.wo, res.get()))) return rc;
+  const KernelSpan spans[1] = {{op == 6 ? "k_bsi_range" : "k_bsi_chain", 0, 1, op == 6 ? 2ull * nk : nk}};
+  if ((rc = stats_end(ctx, nk, 0, spans, 1))) return rc;
+  keyed_result_count(ctx, res.get());
+  *out = res.release();
   return RB_OK;
 }
 
@@ -1019,14 +969,12 @@ int bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *foun
   const uint32_t nbits = bsi->nb - 1;
   hipStream_t st = ctx->stream;
   stats_begin(ctx);
+  Scratch w(ctx->pool);
   BsiKeys ks;
-  int rc = bsi_keys(ctx, bsi, nbits, found, key_lo, key_hi, ks);
+  int rc = bsi_keys(ctx, w, bsi, nbits, found, key_lo, key_hi, ks);
   if (rc) return rc;
   uint64_t *acc = nullptr; // [kStripes][kAccRow], then the folded nbits + 1 words
-  if (ctx->pool.alloc((void **)&acc, (kStripes + 1ull) * kAccRow * 8)) {
-    ks.release(ctx);
-    return fail(RB_ENOMEM, "bsi slice counts");
-  }
+  if (!w.get(acc, (kStripes + 1ull) * kAccRow)) return fail(RB_ENOMEM, "bsi slice counts");
   uint64_t *folded = acc + kStripes * kAccRow;
   hipError_t e = hipMemsetAsync(acc, 0, (kStripes + 1ull) * kAccRow * 8, st);
   if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
@@ -1038,9 +986,8 @@ int bsi_slice_counts(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *foun
   if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], st);
   // the call's one read-back (stats_end waits for the stream)
   if (e == hipSuccess) e = hipMemcpyAsync(counts, folded, (nbits + 1ull) * 8, hipMemcpyDeviceToHost, st);
-  ctx->pool.release(acc); // stream-ordered: handed out again only to later work on this stream
+  w.give_back(acc); // stream-ordered: handed out again only to later work on this stream
   const uint32_t nk = ks.nk;
-  ks.release(ctx);
   if (e != hipSuccess) return fail(RB_EDEVICE, "bsi slice counts failed: %s", hipGetErrorString(e));
   const KernelSpan spans[1] = {{"k_bsi_sum", 0, -1, nk}};
   return stats_end(ctx, nk, 0, spans, 1);
@@ -1180,26 +1127,17 @@ int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint6
   if (!fcard) return empty_result(ctx, out);                       // null or empty foundSet: new Roaring64Bitmap()
   if (k >= fcard) return rbgpu_set_extract(found, 0, 1, out);      // foundSet itself: here a clone, the same bytes
   if (!k || !nbits) return empty_result(ctx, out);                 // the loop does not run: re stays empty
+  Scratch w(ctx->pool);
   BsiKeys ks;
-  int rc = bsi_keys(ctx, bsi, nbits, found, 0, 65536, ks);
+  int rc = bsi_keys(ctx, w, bsi, nbits, found, 0, 65536, ks);
   if (rc) return rc;
   const uint32_t nk = ks.nk; // >= 1: found is not empty
   const SetView bv = bsi->view(), fv = found->view();
   uint8_t *img = nullptr;
   uint64_t *counts = nullptr;
-  rbgpu_set *res = nullptr;
   KeyedSlots fin;
-  bool slots = false;
-  auto done = [&](int r) {
-    ctx->pool.release(img);
-    ctx->pool.release(counts);
-    if (slots) fin.release(ctx, false);
-    ks.release(ctx);
-    if (r && res) rbgpu_set_free(res);
-    return r;
-  };
-  if (ctx->pool.alloc((void **)&img, (uint64_t)nk * kBitmapBytes) || ctx->pool.alloc((void **)&counts, 64 * 8))
-    return done(fail(RB_ENOMEM, "bsi topK candidates of %u keys", nk));
+  if (!w.get(img, (uint64_t)nk * kBitmapBytes) || !w.get(counts, 64))
+    return fail(RB_ENOMEM, "bsi topK candidates of %u keys", nk);
   // ---- phase A: one launch per slice, no host wait in between; one read-back of the counts
   hipError_t e = hipMemsetAsync(counts, 0, 64 * 8, st);
   if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
@@ -1211,7 +1149,7 @@ int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint6
   if (e == hipSuccess) e = hipMemcpyAsync(hc, counts, 64 * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi topK descent failed: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(RB_EDEVICE, "bsi topK descent failed: %s", hipGetErrorString(e));
   // the decisions, as the kernels replayed them (Roaring64BitmapSliceIndex.java:582-592)
   uint64_t pred = 0, kk = k, cand = fcard;
   int stop = (int)nbits;
@@ -1226,28 +1164,20 @@ int bsi_topk(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uint6
     }
   }
   // ---- phase B: every key on its own again
-  res = new rbgpu_set;
-  rc = set_alloc(ctx, res, 1, nk, (uint64_t)nk * kBitmapBytes);
-  if (rc) {
-    delete res;
-    res = nullptr;
-    return done(rc);
-  }
-  rc = fin.alloc(ctx, nk, false);
-  slots = true;
-  if (rc) return done(rc);
-  if (hipEventRecord(ctx->ev[3], st) != hipSuccess) return done(fail(RB_EDEVICE, "event record failed"));
+  SetPtr res;
+  if ((rc = make_set(ctx, 1, nk, (uint64_t)nk * kBitmapBytes, res)) || (rc = fin.alloc(w, nk, false))) return rc;
+  if (hipEventRecord(ctx->ev[3], st) != hipSuccess) return fail(RB_EDEVICE, "event record failed");
   k_bsi_topk_emit<<<nblk(nk, 4), 256, 0, st>>>(bv, fv, bsi->bsi_table, nbits, pred, stop, ks.d_klist, nk, res->payload,
                                                fin.wo, ctx->d_stats);
-  if (hipEventRecord(ctx->ev[4], st) != hipSuccess) return done(fail(RB_EDEVICE, "event record failed"));
-  rc = compact_keyed(ctx, ks.d_klist, nk, fin.wo, res);
+  if (hipEventRecord(ctx->ev[4], st) != hipSuccess) return fail(RB_EDEVICE, "event record failed");
+  rc = compact_keyed(ctx, ks.d_klist, nk, fin.wo, res.get());
   const KernelSpan spans[2] = {{"k_bsi_topk_count", -1, -1, (uint64_t)nk * nbits},
                                {"k_bsi_topk_emit", 0, 1, nk, ctx->ev[3], ctx->ev[4]}};
   if (!rc) rc = stats_end(ctx, nk, 0, spans, 2);
-  if (rc) return done(rc);
-  keyed_result_count(ctx, res);
-  *out = res;
-  return done(RB_OK);
+  if (rc) return rc;
+  keyed_result_count(ctx, res.get());
+  *out = res.release();
+  return RB_OK;
 }
 
 // ---------------------------------------------------------------- value read-back: toPairList and getValue
@@ -1519,25 +1449,16 @@ int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uin
   const bool count_only = !cols && !vals;
   *count = 0;
   stats_begin(ctx);
+  Scratch w(ctx->pool);
   BsiKeys ks;
-  int rc = bsi_keys(ctx, bsi, nbits, found, key_lo, key_hi, ks);
+  int rc = bsi_keys(ctx, w, bsi, nbits, found, key_lo, key_hi, ks);
   if (rc) return rc;
   const uint32_t nk = ks.nk;
   uint64_t *cnt = nullptr, *offs = nullptr, *tmp = nullptr;
   uint32_t *d_cols = host_dst ? nullptr : cols;
   uint64_t *d_vals = host_dst ? nullptr : vals;
-  auto done = [&](int r) {
-    for (void *p : {(void *)cnt, (void *)offs, (void *)tmp}) ctx->pool.release(p);
-    if (host_dst) {
-      ctx->pool.release(d_cols);
-      ctx->pool.release(d_vals);
-    }
-    ks.release(ctx);
-    return r;
-  };
-  if (ctx->pool.alloc((void **)&cnt, (nk + 1ull) * 8) || ctx->pool.alloc((void **)&offs, (nk + 2ull) * 8) ||
-      ctx->pool.alloc((void **)&tmp, (scan_tmp_words(nk) + 1) * 8))
-    return done(fail(RB_ENOMEM, "bsi values: counts of %u keys", nk));
+  if (!w.get(cnt, nk + 1ull) || !w.get(offs, nk + 2ull) || !w.get(tmp, scan_tmp_words(nk) + 1))
+    return fail(RB_ENOMEM, "bsi values: counts of %u keys", nk);
   const SetView bv = bsi->view(), fv = found ? found->view() : bv;
   const int hf = found != nullptr;
   auto gather = [&]() { // phase B, between its own events
@@ -1571,19 +1492,19 @@ int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uin
     if (e == hipSuccess) e = hipGetLastError();
     total = ctx->h_pinned[0];
   }
-  if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi values failed: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(RB_EDEVICE, "bsi values failed: %s", hipGetErrorString(e));
   *count = total;
   if (!count_only && total > cap)
-    return done(fail(RB_EINVAL, "bsi values: %llu pairs exceed the capacity %llu", (unsigned long long)total,
-                     (unsigned long long)cap));
+    return fail(RB_EINVAL, "bsi values: %llu pairs exceed the capacity %llu", (unsigned long long)total,
+                (unsigned long long)cap);
   if (!count_only && host_dst && total) { // host outputs: the buffers take the count the read-back gave
-    if (ctx->pool.alloc((void **)&d_cols, total * 4) || ctx->pool.alloc((void **)&d_vals, total * 8))
-      return done(fail(RB_ENOMEM, "bsi values: %llu pairs", (unsigned long long)total));
+    if (!w.get(d_cols, total) || !w.get(d_vals, total))
+      return fail(RB_ENOMEM, "bsi values: %llu pairs", (unsigned long long)total);
     e = gather();
     gathered = true;
     if (e == hipSuccess) e = hipMemcpyAsync(cols, d_cols, total * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(vals, d_vals, total * 8, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi values failed: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(RB_EDEVICE, "bsi values failed: %s", hipGetErrorString(e));
   }
   const KernelSpan spans[2] = {{"k_bsi_values", 0, 1, nk, ctx->ev[3], ctx->ev[4]},
                                {"k_bsi_values_count", -1, -1, nk, ctx->ev[1], ctx->ev[2]}};
@@ -1594,7 +1515,7 @@ int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uin
     s.main_kernel_bytes = s.kernel_bytes[0];
     std::snprintf(s.main_kernel, sizeof s.main_kernel, "%s", s.kernel_name[0]);
   }
-  return done(rc);
+  return rc;
 }
 
 int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n, uint64_t *values,
@@ -1604,16 +1525,12 @@ int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns
   stats_begin(ctx);
   int rc = ensure_bsi_tables(ctx, bsi, nbits);
   if (rc) return rc;
+  Scratch w(ctx->pool);
   uint32_t *d_c = nullptr;
   uint64_t *d_v = nullptr;
   uint8_t *d_e = nullptr;
-  auto done = [&](int r) {
-    for (void *p : {(void *)d_c, (void *)d_v, (void *)d_e}) ctx->pool.release(p);
-    return r;
-  };
-  if (n && (ctx->pool.alloc((void **)&d_c, n * 4) || (values && ctx->pool.alloc((void **)&d_v, n * 8)) ||
-            (exists && ctx->pool.alloc((void **)&d_e, n))))
-    return done(fail(RB_ENOMEM, "bsi lookups of %llu columns", (unsigned long long)n));
+  if (n && (!w.get(d_c, n) || (values && !w.get(d_v, n)) || (exists && !w.get(d_e, n))))
+    return fail(RB_ENOMEM, "bsi lookups of %llu columns", (unsigned long long)n);
   hipError_t e = n ? hipMemcpyAsync(d_c, columns, n * 4, hipMemcpyHostToDevice, st) : hipSuccess;
   if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
   if (e == hipSuccess && n)
@@ -1622,12 +1539,12 @@ int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns
   if (e == hipSuccess) e = hipEventRecord(ctx->ev[2], st);
   if (e == hipSuccess && n && values) e = hipMemcpyAsync(values, d_v, n * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && n && exists) e = hipMemcpyAsync(exists, d_e, n, hipMemcpyDeviceToHost, st);
-  if (e != hipSuccess) return done(fail(RB_EDEVICE, "bsi lookups failed: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(RB_EDEVICE, "bsi lookups failed: %s", hipGetErrorString(e));
   const KernelSpan spans[1] = {{"k_bsi_get", -1, -1, n}};
-  return done(stats_end(ctx, n, 0, spans, n ? 1 : 0));
+  return stats_end(ctx, n, 0, spans, n ? 1 : 0);
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_bsi() {}
 void warm_bsi(hipStream_t st) { k_warm_bsi<<<1, 64, 0, st>>>(); }
 

@@ -308,45 +308,17 @@ namespace {
 unsigned nblk(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 unsigned grid_for(uint64_t n, unsigned per) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(nblk(n, per), 1), kMaxBlocks); }
 
-// the call's temporaries, back to the pool when the call leaves (every path has waited for the stream, or failed)
-struct Temps {
-  DevPool &pool;
-  std::vector<void *> held;
-  explicit Temps(DevPool &p) : pool(p) {}
-  ~Temps() {
-    for (void *p : held) pool.release(p);
-  }
-  template <class T> bool take(T **p, uint64_t count) {
-    void *q = nullptr;
-    if (pool.alloc(&q, std::max<uint64_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
-    held.push_back(q);
-    *p = static_cast<T *>(q);
-    return true;
-  }
-};
-
 // a set of nb bitmaps without containers
 int empty_set(rbgpu_ctx *ctx, uint32_t nb, rbgpu_set **out) {
-  rbgpu_set *s = new rbgpu_set;
-  int rc = set_alloc(ctx, s, nb, 0, 0);
-  if (rc) {
-    delete s;
-    return rc;
-  }
+  SetPtr s;
+  int rc = make_set(ctx, nb, 0, 0, s);
+  if (rc) return rc;
   stats_begin(ctx);
-  if (hipMemsetAsync(s->begin, 0, (nb + 1ull) * 8, ctx->stream) != hipSuccess) {
-    set_release(s);
-    delete s;
+  if (hipMemsetAsync(s->begin, 0, (nb + 1ull) * 8, ctx->stream) != hipSuccess)
     return fail(RB_EDEVICE, "value build: memset failed");
-  }
   s->h_begin.assign((size_t)nb + 1, 0);
-  rc = stats_end(ctx, 0, 0, nullptr, 0);
-  if (rc) {
-    set_release(s);
-    delete s;
-    return rc;
-  }
-  *out = s;
+  if ((rc = stats_end(ctx, 0, 0, nullptr, 0))) return rc;
+  *out = s.release();
   return RB_OK;
 }
 
@@ -357,13 +329,13 @@ struct Discovery {
   uint64_t tiles = 0, G = 0;
   uint64_t *tile_pre = nullptr;
 };
-int discover(rbgpu_ctx *ctx, Temps &tmp, const BuildSrc &src, uint32_t *d_flag, uint32_t *unsorted, Discovery &d) {
+int discover(rbgpu_ctx *ctx, Scratch &tmp, const BuildSrc &src, uint32_t *d_flag, uint32_t *unsorted, Discovery &d) {
   hipStream_t st = ctx->stream;
   d.tiles = (src.n + kTile - 1) / kTile;
   if (d.tiles >= (1ull << 31)) return fail(RB_EINVAL, "value build: %llu elements in one call", (unsigned long long)src.n);
   uint64_t *tile_heads, *scan_tmp;
-  if (!tmp.take(&tile_heads, d.tiles) || !tmp.take(&d.tile_pre, d.tiles + 1) ||
-      !tmp.take(&scan_tmp, scan_tmp_words(d.tiles) + 1))
+  if (!tmp.get(tile_heads, d.tiles) || !tmp.get(d.tile_pre, d.tiles + 1) ||
+      !tmp.get(scan_tmp, scan_tmp_words(d.tiles) + 1))
     return fail(RB_ENOMEM, "value build: discovery of %llu elements", (unsigned long long)src.n);
   k_build_count_heads<<<(unsigned)d.tiles, 256, 0, st>>>(src, tile_heads, d_flag);
   scan_exclusive(tile_heads, d.tile_pre, d.tiles, scan_tmp, st);
@@ -377,7 +349,7 @@ int discover(rbgpu_ctx *ctx, Temps &tmp, const BuildSrc &src, uint32_t *d_flag, 
 // From the discovered stream to the set: the containers' starts and keys, the measuring pass, the layout, the
 // emitting pass.  d_offs: plain sets' element offsets on the device ([nb + 1]); null: a BSI of nb = nsl bitmaps.
 // stats_begin has been called.
-int build_grouped(rbgpu_ctx *ctx, Temps &tmp, const BuildSrc &src, const Discovery &d, const uint64_t *d_offs,
+int build_grouped(rbgpu_ctx *ctx, Scratch &tmp, const BuildSrc &src, const Discovery &d, const uint64_t *d_offs,
                   uint32_t nb, uint32_t nsl, uint32_t flags, uint64_t in_bytes, rbgpu_set **out) {
   hipStream_t st = ctx->stream;
   const uint64_t tiles = d.tiles, G = d.G;
@@ -386,9 +358,9 @@ int build_grouped(rbgpu_ctx *ctx, Temps &tmp, const BuildSrc &src, const Discove
   uint64_t *cstart, *tkeep, *tbytes, *tpos, *toff, *scan_tmp2;
   uint16_t *ckey;
   uint8_t *ttype;
-  if (!tmp.take(&cstart, G + 1) || !tmp.take(&ckey, G) || !tmp.take(&ttype, T) || !tmp.take(&tkeep, T) ||
-      !tmp.take(&tbytes, T) || !tmp.take(&tpos, T + 1) || !tmp.take(&toff, T + 1) ||
-      !tmp.take(&scan_tmp2, scan_tmp_words(T) + 1))
+  if (!tmp.get(cstart, G + 1) || !tmp.get(ckey, G) || !tmp.get(ttype, T) || !tmp.get(tkeep, T) ||
+      !tmp.get(tbytes, T) || !tmp.get(tpos, T + 1) || !tmp.get(toff, T + 1) ||
+      !tmp.get(scan_tmp2, scan_tmp_words(T) + 1))
     return fail(RB_ENOMEM, "value build: workspace of %llu containers", (unsigned long long)T);
   k_build_write_heads<<<(unsigned)tiles, 256, 0, st>>>(src, tile_pre, cstart, ckey);
   BuildArgs a{};
@@ -417,16 +389,11 @@ int build_grouped(rbgpu_ctx *ctx, Temps &tmp, const BuildSrc &src, const Discove
   HIPCHK(hipStreamSynchronize(st));
   LAUNCHCHK();
   const uint64_t nc = tot[0], total = tot[1];
-  rbgpu_set *s = new rbgpu_set;
-  int rc = set_alloc(ctx, s, nb, nc, total);
-  if (rc) {
-    delete s;
-    return rc;
-  }
-  auto drop = [&](int r) {
+  SetPtr s;
+  int rc = make_set(ctx, nb, nc, total, s);
+  if (rc) return rc;
+  auto drop = [&](int r) { // the set goes back to the pool behind its kernels
     (void)hipStreamSynchronize(st);
-    set_release(s);
-    delete s;
     return r;
   };
   if (d_offs) k_build_begin<<<nblk(nb + 1ull, 256), 256, 0, st>>>(cstart, G, d_offs, nb, s->begin);
@@ -440,7 +407,7 @@ int build_grouped(rbgpu_ctx *ctx, Temps &tmp, const BuildSrc &src, const Discove
   const KernelSpan spans[2] = {{"k_set_build", 0, -1, T}, {"k_set_build", 0, 1, nc, ctx->ev[3], ctx->ev[4]}};
   rc = stats_end(ctx, nc, nc, spans, 2);
   if (rc) return drop(rc);
-  *out = s;
+  *out = s.release();
   return RB_OK;
 }
 } // namespace
@@ -451,13 +418,13 @@ int build_set_values(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *o
   const uint64_t base = nb ? offsets[0] : 0, n = nb ? offsets[nb] - base : 0;
   if (!n) return empty_set(ctx, nb, out);
   hipStream_t st = ctx->stream;
-  Temps tmp(ctx->pool);
+  Scratch tmp(ctx->pool); // back to the pool when the call leaves (every path has waited for the stream, or failed)
   std::vector<uint64_t> rel((size_t)nb + 1);
   for (uint32_t i = 0; i <= nb; ++i) rel[i] = offsets[i] - base;
   uint64_t *d_offs;
   uint32_t *flag, *starts;
   const uint64_t start_words = n / 32 + 1;
-  if (!tmp.take(&d_offs, nb + 1ull) || !tmp.take(&starts, start_words) || !tmp.take(&flag, 1))
+  if (!tmp.get(d_offs, nb + 1ull) || !tmp.get(starts, start_words) || !tmp.get(flag, 1))
     return fail(RB_ENOMEM, "value build: %llu values", (unsigned long long)n);
   stats_begin(ctx);
   HIPCHK(hipMemcpyAsync(d_offs, rel.data(), (nb + 1ull) * 8, hipMemcpyHostToDevice, st));
@@ -477,7 +444,7 @@ int build_set_values(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *o
     uint64_t *keys, *sorted;
     uint8_t *stmp;
     HIPCHK(build_sort_keys(nullptr, &bytes, nullptr, nullptr, n, 16, end_bit, st));
-    if (!tmp.take(&keys, n) || !tmp.take(&sorted, n) || !tmp.take(&stmp, bytes))
+    if (!tmp.get(keys, n) || !tmp.get(sorted, n) || !tmp.get(stmp, bytes))
       return fail(RB_ENOMEM, "value build: sort of %llu values", (unsigned long long)n);
     k_build_keys<<<grid_for(n, 256), 256, 0, st>>>(d_values + base, d_offs, nb, n, keys);
     HIPCHK(build_sort_keys(stmp, &bytes, keys, sorted, n, 16, end_bit, st));
@@ -494,10 +461,10 @@ int build_bsi_pairs(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_va
   if (max_value) *max_value = 0;
   if (!n) return empty_set(ctx, 1, out);
   hipStream_t st = ctx->stream;
-  Temps tmp(ctx->pool);
+  Scratch tmp(ctx->pool); // back to the pool when the call leaves (every path has waited for the stream, or failed)
   uint32_t *flag;
   uint64_t *mm;
-  if (!tmp.take(&flag, 1) || !tmp.take(&mm, 2)) return fail(RB_ENOMEM, "BSI build");
+  if (!tmp.get(flag, 1) || !tmp.get(mm, 2)) return fail(RB_ENOMEM, "BSI build");
   stats_begin(ctx);
   const uint64_t mm0[2] = {~0ull, 0ull};
   HIPCHK(hipMemsetAsync(flag, 0, 4, st));
@@ -516,7 +483,7 @@ int build_bsi_pairs(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_va
     uint64_t *sval;
     uint8_t *stmp;
     HIPCHK(build_sort_pairs(nullptr, &bytes, d_cols, nullptr, d_vals, nullptr, n, st));
-    if (!tmp.take(&scol, n) || !tmp.take(&sval, n) || !tmp.take(&stmp, bytes))
+    if (!tmp.get(scol, n) || !tmp.get(sval, n) || !tmp.get(stmp, bytes))
       return fail(RB_ENOMEM, "BSI build: sort of %llu pairs", (unsigned long long)n);
     HIPCHK(build_sort_pairs(stmp, &bytes, d_cols, scol, d_vals, sval, n, st));
     cols = scol;
@@ -538,7 +505,7 @@ int build_bsi_pairs(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_va
   return RB_OK;
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_build() {}
 void warm_build(hipStream_t st) { k_warm_build<<<1, 64, 0, st>>>(); }
 

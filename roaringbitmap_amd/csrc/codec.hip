@@ -441,20 +441,6 @@ __global__ __launch_bounds__(256) void k_ser_owner(SerArgs a, uint32_t *owner) {
 
 uint32_t grid_for(uint64_t waves) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((waves + kWaves - 1) / kWaves, 1), 1u << 20); }
 
-struct Scratch { // pool allocations released together
-  DevPool &pool;
-  std::vector<void *> held;
-  explicit Scratch(DevPool &p) : pool(p) {}
-  ~Scratch() {
-    for (void *p : held) pool.release(p);
-  }
-  template <class T> bool get(T *&p, uint64_t n) {
-    if (pool.alloc((void **)&p, std::max<uint64_t>(n, 1) * sizeof(T))) return false;
-    held.push_back(p);
-    return true;
-  }
-};
-
 int report_error(uint64_t e) {
   const uint32_t b = (uint32_t)(e >> 25), cls = (e >> 24) & 1, k = (e >> 8) & 0xFFFF, why = e & 0xFF;
   const char *txt = why < kReasons ? kReasonText[why] : "?";
@@ -507,13 +493,9 @@ int deserialize_device(rbgpu_ctx *ctx, const uint8_t *d_in, uint64_t in_lim, con
   HIPCHK(hipStreamSynchronize(st));
   LAUNCHCHK();
   const uint64_t small_base = tot[0] * kBitmapBytes, total = small_base + tot[1];
-  rbgpu_set *s = new rbgpu_set;
-  int rc = set_alloc(ctx, s, n, nc, total);
-  if (rc) {
-    set_release(s);
-    delete s;
-    return rc;
-  }
+  SetPtr s;
+  const int rc = make_set(ctx, n, nc, total, s);
+  if (rc) return rc;
   launch_layout(a.bigflag, bidx, soff, small_base, s->off, nc, st);
   if (nc) k_de_copy<<<grid_for(nc), 256, 0, st>>>(a, nc, s->off, s->payload);
   auto cp = [&](void *dst, const void *src, size_t bytes) {
@@ -522,17 +504,10 @@ int deserialize_device(rbgpu_ctx *ctx, const uint8_t *d_in, uint64_t in_lim, con
   uint64_t e = ~0ull;
   if (cp(s->begin, cbase, (n + 1ull) * 8) || cp(s->key, a.key, nc * 2) || cp(s->type, a.type, nc) ||
       cp(s->card, a.card, nc * 4) || cp(s->nruns, a.nruns, nc * 2) ||
-      hipMemcpyAsync(&e, err, 8, hipMemcpyDeviceToHost, st) || hipStreamSynchronize(st)) {
-    set_release(s);
-    delete s;
+      hipMemcpyAsync(&e, err, 8, hipMemcpyDeviceToHost, st) || hipStreamSynchronize(st))
     return fail(RB_EDEVICE, "device deserialize failed");
-  }
-  if (e != ~0ull) {
-    set_release(s);
-    delete s;
-    return report_error(e);
-  }
-  *out = s;
+  if (e != ~0ull) return report_error(e);
+  *out = s.release();
   return RB_OK;
 }
 
@@ -579,7 +554,7 @@ int serialize_device(const rbgpu_set *s, uint32_t first, uint32_t count, uint8_t
   return RB_OK;
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_codec() {}
 void warm_codec(hipStream_t st) { k_warm_codec<<<1, 64, 0, st>>>(); }
 

@@ -511,19 +511,16 @@ int gather(rbgpu_comm *c, const ShardSrc *src, const rb_shard_summary *summary, 
   std::vector<uint8_t> h_stage;
   Part *d_parts = nullptr;
   uint8_t *d_out = nullptr; // device assembly into a host dst
+  DevPool no_pool;          // a host transport takes no device scratch (and may have no context)
+  Scratch w(dev ? ctx->pool : no_pool);
   if (dev) {
-    if (ctx->pool.alloc((void **)&d_stage, std::max<uint64_t>(stage, 16))) {
-      d_stage = nullptr;
-      local_rc = fail(RB_ENOMEM, "gather staging");
-    }
+    if (!w.get(d_stage, stage)) local_rc = fail(RB_ENOMEM, "gather staging");
   } else {
     h_stage.assign(std::max<uint64_t>(stage, 16), 0);
   }
   uint8_t *stage_p = dev ? d_stage : h_stage.data();
-  auto done = [&](int code) { // every pooled buffer goes back on every path
+  auto done = [&](int code) { // the pooled buffers go back behind the stream's work, on every path
     if (st) (void)hipStreamSynchronize(st);
-    for (void *p : {(void *)d_stage, (void *)d_parts, (void *)d_out})
-      if (p) ctx->pool.release(p);
     return code;
   };
   uint8_t *mine_at = stage_p ? stage_p + (is_root ? base[c->rank] : 0) : nullptr;
@@ -567,16 +564,10 @@ int gather(rbgpu_comm *c, const ShardSrc *src, const rb_shard_summary *summary, 
   if (dev) {
     uint8_t *out = dst;
     if (!dst_device) {
-      if (ctx->pool.alloc((void **)&d_out, std::max<uint64_t>(total, 16))) {
-        d_out = nullptr;
-        return done(fail(RB_ENOMEM, "assembly buffer"));
-      }
+      if (!w.get(d_out, total)) return done(fail(RB_ENOMEM, "assembly buffer"));
       out = d_out;
     }
-    if (ctx->pool.alloc((void **)&d_parts, sizeof(Part) * parts.size())) {
-      d_parts = nullptr;
-      return done(fail(RB_ENOMEM, "gather plan"));
-    }
+    if (!w.get(d_parts, parts.size())) return done(fail(RB_ENOMEM, "gather plan"));
     if (hipMemcpyAsync(d_parts, parts.data(), sizeof(Part) * parts.size(), hipMemcpyHostToDevice, st))
       return done(fail(RB_EDEVICE, "gather plan upload"));
     const uint64_t items = assemble_items(gl);

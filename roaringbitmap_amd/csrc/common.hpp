@@ -53,7 +53,7 @@ __host__ __device__ inline uint32_t desc_card(uint32_t d) { return d >> 2; }
 // with the counters so the call needs one device-to-host copy.
 constexpr int kStatWords = 9, kStripes = 64;
 
-// FastAggregation.priorityqueue_or's intermediate bitmaps (api.hip pq_or) carry two marks in the card
+// FastAggregation.priorityqueue_or's intermediate bitmaps (aggregate.hip pq_or) carry two marks in the card
 // word of their containers, never seen outside that call: a lazy Bitmap (the reference's cardinality
 // -1 after a lazy OR) and a Run kept as 8 KiB of bitmap words (a lazily merged Run of 2048..4096 runs,
 // RunContainer.lazyorToRun, whose run list would not fit an 8 KiB slot).

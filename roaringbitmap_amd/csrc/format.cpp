@@ -145,12 +145,8 @@ int parse_serialized(const uint8_t *buf, uint64_t len, HostSoA &out, std::string
   return RB_OK;
 }
 
-static uint64_t container_bytes(const HostSoA &s, uint64_t i) { // Container.getArraySizeInBytes
-  switch (s.type[i]) {
-  case RB_ARRAY: return 2ull * s.card[i];
-  case RB_BITMAP: return 8192;
-  default: return 2 + 4ull * s.nruns[i];
-  }
+static uint64_t container_bytes(const HostSoA &s, uint64_t i) {
+  return serialized_container_bytes(s.type[i], s.card[i], s.nruns[i]);
 }
 
 uint64_t serialized_size(const HostSoA &s, uint32_t b) {
@@ -161,8 +157,7 @@ uint64_t serialized_size(const HostSoA &s, uint32_t b) {
     hasrun |= s.type[i] == RB_RUN;
     bytes += container_bytes(s, i);
   }
-  uint64_t h = hasrun ? (n < kNoOffsetThreshold ? 4 + (n + 7) / 8 + 4 * n : 4 + (n + 7) / 8 + 8 * n) : 8 + 8 * n;
-  return h + bytes;
+  return serialized_header_bytes(hasrun, n) + bytes;
 }
 
 void serialize_bitmap(const HostSoA &s, uint32_t b, uint8_t *dst) {

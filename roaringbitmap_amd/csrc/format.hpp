@@ -29,6 +29,15 @@ int parse_serialized(const uint8_t *buf, uint64_t len, HostSoA &out, std::string
 // Check one container of a host SoA for the canonical form the engine relies on.
 int validate_container(uint16_t type, uint32_t card, uint32_t nruns, const uint8_t *payload, std::string &err);
 
+// A container's serialized bytes (Container.getArraySizeInBytes; types: RB_ARRAY 0, RB_BITMAP 1, RB_RUN 2) and
+// the header in front of a bitmap's n containers (RoaringArray.java:851-870; no offsets below 4 with a Run).
+inline uint64_t serialized_container_bytes(int type, uint32_t card, uint32_t nruns) {
+  return type == 0 ? 2ull * card : type == 1 ? 8192ull : 2 + 4ull * nruns;
+}
+inline uint64_t serialized_header_bytes(bool hasrun, uint64_t n) {
+  return hasrun ? (n < 4 ? 4 + (n + 7) / 8 + 4 * n : 4 + (n + 7) / 8 + 8 * n) : 8 + 8 * n;
+}
+
 // RoaringArray.serializedSizeInBytes / serialize (RoaringArray.java:851-953) for bitmap b.
 uint64_t serialized_size(const HostSoA &s, uint32_t b);
 void serialize_bitmap(const HostSoA &s, uint32_t b, uint8_t *dst);

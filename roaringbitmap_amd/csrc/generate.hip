@@ -169,7 +169,7 @@ void launch_gen_emit(const GenSpec &g, uint64_t n, const uint8_t *type, const ui
   k_gen_emit<<<(unsigned)std::min<uint64_t>((n + 3) / 4, 1u << 20), 256, 0, st>>>(g, n, type, off, payload);
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_generate() {}
 void warm_generate(hipStream_t st) { k_warm_generate<<<1, 64, 0, st>>>(); }
 
@@ -284,27 +284,19 @@ int materialize(rbgpu_ctx *ctx, const GenStructure &gs, uint64_t seed, rbgpu_set
   hipStream_t st = ctx->stream;
   DevPool &pool = ctx->pool;
   const uint64_t n = gs.key.size();
-  rbgpu_set *s = new rbgpu_set;
-  int rc = set_alloc(ctx, s, gs.nb, n, 16);
-  if (rc) {
-    delete s;
-    return rc;
-  }
+  Scratch w(pool);
+  SetPtr s;
+  const int rc = make_set(ctx, gs.nb, n, 16, s);
+  if (rc) return rc;
   uint8_t *d_target;
   uint32_t *d_param;
   uint64_t *d_uid;
   uint64_t *d_big, *d_small, *d_bidx, *d_soff, *d_tmp;
   const uint64_t tmpw = std::max<uint64_t>(scan_tmp_words(n + 1), 1);
   const uint64_t nn = std::max<uint64_t>(n, 1);
-  if (pool.alloc((void **)&d_target, nn) || pool.alloc((void **)&d_param, nn * 4) ||
-      pool.alloc((void **)&d_uid, nn * 8) ||
-      pool.alloc((void **)&d_big, (nn + 1) * 8) || pool.alloc((void **)&d_small, (nn + 1) * 8) ||
-      pool.alloc((void **)&d_bidx, (nn + 1) * 8) || pool.alloc((void **)&d_soff, (nn + 1) * 8) ||
-      pool.alloc((void **)&d_tmp, tmpw * 8)) {
-    set_release(s);
-    delete s;
+  if (!w.get(d_target, nn) || !w.get(d_param, nn) || !w.get(d_uid, nn) || !w.get(d_big, nn + 1) ||
+      !w.get(d_small, nn + 1) || !w.get(d_bidx, nn + 1) || !w.get(d_soff, nn + 1) || !w.get(d_tmp, tmpw))
     return fail(RB_ENOMEM, "generator workspace for %llu containers", (unsigned long long)n);
-  }
   HIPCHK(hipMemcpyAsync(s->begin, gs.begin.data(), (gs.nb + 1) * 8, hipMemcpyHostToDevice, st));
   if (n) {
     HIPCHK(hipMemcpyAsync(s->key, gs.key.data(), n * 2, hipMemcpyHostToDevice, st));
@@ -323,22 +315,17 @@ int materialize(rbgpu_ctx *ctx, const GenStructure &gs, uint64_t seed, rbgpu_set
   LAUNCHCHK();
   const uint64_t small_base = tot[0] * kBitmapBytes, total = small_base + tot[1];
   launch_layout(d_big, d_bidx, d_soff, small_base, s->off, n, st);
-  pool.release(s->payload);
+  pool.release(s->payload); // the placeholder goes back first: the arena is sized only now
   if (pool.alloc((void **)&s->payload, std::max<uint64_t>(total, 16))) {
     s->payload = nullptr;
-    set_release(s);
-    delete s;
     return fail(RB_ENOMEM, "generator payload of %llu bytes", (unsigned long long)total);
   }
   s->payload_bytes = total;
   launch_gen_emit(g, n, s->type, s->off, s->payload, st);
   HIPCHK(hipStreamSynchronize(st));
   LAUNCHCHK();
-  for (void *p : {(void *)d_target, (void *)d_param, (void *)d_uid, (void *)d_big, (void *)d_small, (void *)d_bidx, (void *)d_soff,
-                  (void *)d_tmp})
-    pool.release(p);
   s->h_begin = gs.begin;
-  *out = s;
+  *out = s.release();
   return RB_OK;
 }
 } // namespace
@@ -371,16 +358,12 @@ int generate_sets(rbgpu_ctx *ctx, int workload, uint32_t n, uint64_t seed, uint3
   if (key_lo > key_hi || key_hi > 65536) return fail(RB_EINVAL, "bad key range [%u, %u)", key_lo, key_hi);
   std::vector<GenStructure> gs;
   structure(workload, n, seed, key_lo, key_hi, gs);
-  int rc = materialize(ctx, gs[0], seed * 31 + 1, a);
+  rbgpu_set *first = nullptr;
+  int rc = materialize(ctx, gs[0], seed * 31 + 1, &first);
   if (rc) return rc;
-  if (gs.size() > 1) {
-    rc = materialize(ctx, gs[1], seed * 31 + 2, b);
-    if (rc) {
-      rbgpu_set_free(*a);
-      *a = nullptr;
-      return rc;
-    }
-  }
+  SetPtr owner(first);
+  if (gs.size() > 1 && (rc = materialize(ctx, gs[1], seed * 31 + 2, b))) return rc;
+  *a = owner.release();
   return RB_OK;
 }
 

@@ -2,11 +2,13 @@
 #pragma once
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "common.hpp"
+#include "format.hpp"
 #include "kernels.hpp"
 
 namespace rbg {
@@ -28,9 +30,13 @@ int fail(int code, const char *fmt, ...);
   } while (0)
 
 // Device allocation cache: a freed block is reused for requests in [size/2, size].
+// outstanding: blocks handed out and not yet released (+1 per successful alloc, -1 per release of a block the
+// pool knows), so a leak or a second release of one block leaves it off balance once every set is freed
+// (rbgpu_internal_pool_outstanding).
 struct DevPool {
   std::multimap<size_t, void *> free_;
   std::unordered_map<void *, size_t> size_;
+  int64_t outstanding = 0;
   ~DevPool() { clear(); }
   void clear() {
     for (auto &kv : free_) {
@@ -45,6 +51,7 @@ struct DevPool {
     if (it != free_.end() && it->first <= 2 * n) {
       *p = it->second;
       free_.erase(it);
+      ++outstanding;
       return hipSuccess;
     }
     hipError_t e = hipMalloc(p, n);
@@ -55,12 +62,51 @@ struct DevPool {
       if (e != hipSuccess) return e;
     }
     size_[*p] = n;
+    ++outstanding;
     return hipSuccess;
   }
   void release(void *p) {
     if (!p) return;
     auto it = size_.find(p);
-    if (it != size_.end()) free_.emplace(it->second, p);
+    if (it == size_.end()) return;
+    free_.emplace(it->second, p);
+    --outstanding;
+  }
+};
+
+// A call's pool scratch: typed blocks taken from a DevPool and returned when the guard leaves scope, on every
+// return path.  give_back returns one block early (stream-ordered: the pool hands it only to later work on this
+// stream); keep hands a block that outlives the call to its new owner (a set's derived tables).
+struct Scratch {
+  DevPool &pool;
+  std::vector<void *> held;
+  explicit Scratch(DevPool &p) : pool(p) {}
+  Scratch(const Scratch &) = delete;
+  Scratch &operator=(const Scratch &) = delete;
+  ~Scratch() {
+    for (void *p : held) pool.release(p);
+  }
+  template <class T> bool get(T *&p, uint64_t n) { // n elements (at least one)
+    void *q = nullptr;
+    if (pool.alloc(&q, std::max<uint64_t>(n, 1) * sizeof(T)) != hipSuccess) return false;
+    held.push_back(q);
+    p = static_cast<T *>(q);
+    return true;
+  }
+  void give_back(void *p) {
+    if (drop(p)) pool.release(p);
+  }
+  template <class T> T *keep(T *p) {
+    drop(p);
+    return p;
+  }
+
+private:
+  bool drop(void *p) {
+    auto it = std::find(held.begin(), held.end(), p);
+    if (!p || it == held.end()) return false;
+    held.erase(it);
+    return true;
   }
 };
 
@@ -247,8 +293,40 @@ struct rbgpu_set {
 
 namespace rbg {
 int set_alloc(rbgpu_ctx *ctx, rbgpu_set *s, uint32_t nb, uint64_t nc, uint64_t payload);
-// the pairwise pipeline with its flags (api.hip): x1.op(x2) in place (PairArgs::inplace), XOR results
-// kept when empty (TaskMeta::keep_empty); a_idx / b_idx may hold kEmptyBitmap
+// A result set under construction: freed (rbgpu_set_free) on every return path until its producer hands it
+// to the caller with release().  make_set: a new set with its seven arrays, nothing left behind on failure.
+struct SetFree {
+  void operator()(rbgpu_set *s) const { rbgpu_set_free(s); }
+};
+using SetPtr = std::unique_ptr<rbgpu_set, SetFree>;
+int make_set(rbgpu_ctx *ctx, uint32_t nb, uint64_t nc, uint64_t payload, SetPtr &out);
+// context.hip: a non-null context, its device current, earlier launch errors cleared
+int check_ctx(rbgpu_ctx *ctx);
+// pinned staging (ctx->h_stage) of at least `bytes`
+int ensure_stage(rbgpu_ctx *ctx, size_t bytes);
+// set.hip: a validated host SoA as a new set / bitmaps [first, first + count) back to the host
+int upload_host(rbgpu_ctx *ctx, const HostSoA &h, rbgpu_set **out);
+int download_host(const rbgpu_set *s, uint32_t first, uint32_t count, HostSoA &h);
+// set.hip: type / nruns / card (and key, when asked for) of containers [lo, lo + n) on the host
+int read_meta(const rbgpu_set *s, uint64_t lo, uint64_t n, std::vector<uint8_t> &type, std::vector<uint16_t> &nruns,
+              std::vector<uint32_t> &card, std::vector<uint16_t> *key = nullptr);
+// The pairwise pipeline (pairwise_call.hip) and what its entry points vary:
+//   probe       0 = the product path; 1 / 2 = measurement probes (rbgpu_internal_probe) in place of the task
+//               kernel — results are not produced
+//   inplace     x1.op(x2) in place (PairArgs::inplace)
+//   keep_empty  XOR results kept when empty (TaskMeta::keep_empty)
+//   async       return once the task kernels and the compaction are enqueued (rbgpu_pairwise_async): the result
+//               is pending (settle() fills its container count), the call's counters are not read back (rb_stats
+//               keeps the last synchronous call's), and `ext` (if any, another stream of the caller) is ordered
+//               around the call
+struct PairOpts {
+  int probe = 0;
+  bool inplace = false, keep_empty = false, async = false;
+  hipStream_t ext = nullptr;
+};
+// a_idx / b_idx may hold kEmptyBitmap; out null: the per-pair cardinalities only (card_out)
+int pairwise_impl(rbgpu_ctx *ctx, int op, const rbgpu_set *a, const rbgpu_set *b, const uint32_t *a_idx,
+                  const uint32_t *b_idx, uint32_t npairs, rbgpu_set **out, uint64_t *card_out, const PairOpts &o);
 int pairwise_call(rbgpu_ctx *ctx, int op, const rbgpu_set *a, const rbgpu_set *b, const uint32_t *a_idx,
                   const uint32_t *b_idx, uint32_t npairs, rbgpu_set **out, bool inplace, bool keep_empty);
 void ctx_unref(rbgpu_ctx *ctx);
@@ -357,7 +435,7 @@ int build_set_values(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *o
                      rbgpu_set **out);
 int build_bsi_pairs(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_vals, uint64_t n, uint32_t flags,
                     rbgpu_set **out, uint64_t *min_value, uint64_t *max_value);
-// api.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
+// set.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
 int set_key_subset(const rbgpu_set *s, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
 int set_gather(const rbgpu_set *s, const uint32_t *idx, uint32_t n, rbgpu_set **out);
 // codec.hip: RoaringFormatSpec on the device.  d_in is readable up to in_lim; d_in_off[n + 1] (device).

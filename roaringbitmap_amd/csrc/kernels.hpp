@@ -254,6 +254,9 @@ bool launch_wide_runs(int sem, const SetView &s, const uint64_t *mrec, const Cid
 
 // ---- setops.hip
 void launch_bitmap_cards(const SetView &s, uint32_t nbitmaps, uint64_t *out, hipStream_t st);
+// out[i] = containers of member i (members null: bitmap i) with high key in [lo, hi)
+void launch_range_counts(const uint64_t *begin, const uint16_t *key, const uint32_t *members, uint32_t n, uint32_t lo,
+                         uint32_t hi, uint64_t *out, hipStream_t st);
 void launch_gather(const uint8_t *src, const uint64_t *soff, const uint64_t *bytes, uint8_t *dst,
                    const uint64_t *doff, uint64_t n, hipStream_t st);
 void launch_layout(const uint64_t *bigflag, const uint64_t *bidx, const uint64_t *soff, uint64_t small_base,

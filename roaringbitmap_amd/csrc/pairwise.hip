@@ -668,7 +668,7 @@ __global__ __launch_bounds__(kPairThreads) void k_pair_count(PairArgs a, uint64_
 constexpr uint32_t kEmitStage = 640; // records (25 KiB); a block with more stores directly
 // tot (when non-null): the scans' totals on the device (tasks, light, big, small) — the heavy records
 // follow the light ones in one array and the small slots follow the big ones, so the launch needs no
-// host read-back of the totals (api.hip launches it before the host has them)
+// host read-back of the totals (pairwise_call.hip launches it before the host has them)
 // cnt: the segments' counts, bs: the exclusive scans of the block totals (bs.x[blockIdx]); every
 // segment's task offset is also stored in task_begin[p] (task_begin[nseg] = the total) for the
 // compaction.
@@ -2261,7 +2261,7 @@ void launch_pair_small(int op, bool card_only, const SmallPairArgs &a, const Sma
   }
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_pairwise() {}
 void warm_pairwise(hipStream_t st) { k_warm_pairwise<<<1, 64, 0, st>>>(); }
 

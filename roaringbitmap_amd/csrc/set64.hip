@@ -84,19 +84,14 @@ uint64_t blob_len(const uint8_t *p, uint64_t avail) {
 }
 
 rbgpu_set *empty_set(rbgpu_ctx *ctx) {
-  rbgpu_set *s = new rbgpu_set;
-  if (set_alloc(ctx, s, 0, 0, 16)) {
-    delete s;
-    return nullptr;
-  }
+  SetPtr s;
+  if (make_set(ctx, 0, 0, 16, s)) return nullptr;
   const uint64_t z = 0;
   if (hipMemcpyAsync(s->begin, &z, 8, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-      hipStreamSynchronize(ctx->stream) != hipSuccess) {
-    rbgpu_set_free(s);
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
     return nullptr;
-  }
   s->h_begin = {0};
-  return s;
+  return s.release();
 }
 
 uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }

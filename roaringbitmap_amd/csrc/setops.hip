@@ -34,6 +34,30 @@ void launch_gather(const uint8_t *src, const uint64_t *soff, const uint64_t *byt
   k_gather<<<(unsigned)(n < (4ull << 20) ? (n + 3) / 4 : (1u << 20)), 256, 0, st>>>(src, soff, bytes, dst, doff, n);
 }
 
+// containers of each member with high key in [lo, hi): two binary searches over its sorted keys
+extern "C" __global__ void k_range_counts(const uint64_t *begin, const uint16_t *key, const uint32_t *members, uint32_t n,
+                               uint32_t lo, uint32_t hi, uint64_t *out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t m = members ? members[i] : i;
+  const uint64_t b = begin[m], e = begin[m + 1];
+  auto lower = [&](uint32_t k) {
+    uint64_t l = b, h = e;
+    while (l < h) {
+      const uint64_t mid = (l + h) >> 1;
+      if (key[mid] < k) l = mid + 1;
+      else h = mid;
+    }
+    return l;
+  };
+  out[i] = lower(hi) - lower(lo);
+}
+void launch_range_counts(const uint64_t *begin, const uint16_t *key, const uint32_t *members, uint32_t n, uint32_t lo,
+                         uint32_t hi, uint64_t *out, hipStream_t st) {
+  if (!n) return;
+  k_range_counts<<<(n + 255) / 256, 256, 0, st>>>(begin, key, members, n, lo, hi, out);
+}
+
 // Payload layout of generated / uploaded sets: Bitmaps first at 8 KiB strides, then the rest.
 __global__ __launch_bounds__(256) void k_layout(const uint64_t *bigflag, const uint64_t *bidx, const uint64_t *soff,
                                                 uint64_t small_base, uint64_t *off, uint64_t n) {
@@ -114,7 +138,7 @@ void launch_run_optimize(const SetView &s, uint64_t n, uint8_t *type, uint16_t *
   if (nb && any_run) k_any_run<<<(nb + 3) / 4, 256, 0, st>>>(s.begin, type, nb, any_run);
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_setops() {}
 void warm_setops(hipStream_t st) { k_warm_setops<<<1, 64, 0, st>>>(); }
 

@@ -327,26 +327,18 @@ constexpr uint64_t kMaxBlocks = 2048; // 256 CUs x 8 blocks; the rest is grid-st
 static int ensure_card_prefix(const rbgpu_set *cs) {
   rbgpu_set *s = const_cast<rbgpu_set *>(cs);
   if (s->cpre) return RB_OK;
-  DevPool &pool = s->ctx->pool;
+  Scratch w(s->ctx->pool);
   hipStream_t st = s->ctx->stream;
   uint64_t *pre = nullptr, *c64 = nullptr, *tmp = nullptr;
-  if (pool.alloc((void **)&pre, (s->nc + 1) * 8) || pool.alloc((void **)&c64, std::max<uint64_t>(s->nc, 1) * 8) ||
-      pool.alloc((void **)&tmp, (scan_tmp_words(s->nc) + 1) * 8)) {
-    for (void *p : {(void *)pre, (void *)c64, (void *)tmp}) pool.release(p);
+  if (!w.get(pre, s->nc + 1) || !w.get(c64, s->nc) || !w.get(tmp, scan_tmp_words(s->nc) + 1))
     return fail(RB_ENOMEM, "cardinality prefix of %llu containers", (unsigned long long)s->nc);
-  }
   {
     DeriveTimer t(s, -1);
     if (s->nc) k_set_card64<<<(unsigned)std::min<uint64_t>(nblk(s->nc, 256), kMaxBlocks), 256, 0, st>>>(s->card, s->nc, c64);
     scan_exclusive(c64, pre, s->nc, tmp, st);
   } // the timer's end waits for the stream: the scratch is free again
-  pool.release(c64);
-  pool.release(tmp);
-  if (hipGetLastError() != hipSuccess) {
-    pool.release(pre);
-    return fail(RB_EDEVICE, "cardinality-prefix kernels failed");
-  }
-  s->cpre = pre;
+  if (hipGetLastError() != hipSuccess) return fail(RB_EDEVICE, "cardinality-prefix kernels failed");
+  s->cpre = w.keep(pre);
   s->derive_bytes += 12ull * s->nc;
   return RB_OK;
 }
@@ -366,15 +358,10 @@ int set_values(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *dst
   rc = ensure_card_prefix(s);
   if (rc) return rc;
   stats_begin(ctx);
+  Scratch w(ctx->pool);
   uint64_t *d_offs = nullptr;
   uint32_t *d_dst = host_dst ? nullptr : dst;
-  auto done = [&](int r) {
-    ctx->pool.release(d_offs);
-    if (host_dst) ctx->pool.release(d_dst);
-    return r;
-  };
-  if (ctx->pool.alloc((void **)&d_offs, (count + 1ull) * 8))
-    return done(fail(RB_ENOMEM, "value offsets of %u bitmaps", count));
+  if (!w.get(d_offs, count + 1ull)) return fail(RB_ENOMEM, "value offsets of %u bitmaps", count);
   auto decode = [&]() { // between the call's kernel events
     hipError_t e = hipEventRecord(ctx->ev[1], st);
     if (e == hipSuccess) {
@@ -395,21 +382,20 @@ int set_values(const rbgpu_set *s, uint32_t first, uint32_t count, uint32_t *dst
   if (e == hipSuccess) e = hipMemcpyAsync(offsets, d_offs, (count + 1ull) * 8, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return done(fail(RB_EDEVICE, "set values failed: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(RB_EDEVICE, "set values failed: %s", hipGetErrorString(e));
   const uint64_t total = offsets[count];
   if (dst && total > cap)
-    return done(fail(RB_EINVAL, "set values: %llu values exceed the capacity %llu", (unsigned long long)total,
-                     (unsigned long long)cap));
+    return fail(RB_EINVAL, "set values: %llu values exceed the capacity %llu", (unsigned long long)total,
+                (unsigned long long)cap);
   if (dst && host_dst && total) { // host output: the staging buffer takes the size the read-back gave
-    if (ctx->pool.alloc((void **)&d_dst, total * 4))
-      return done(fail(RB_ENOMEM, "set values: %llu values", (unsigned long long)total));
+    if (!w.get(d_dst, total)) return fail(RB_ENOMEM, "set values: %llu values", (unsigned long long)total);
     e = decode();
     decoded = true;
     if (e == hipSuccess) e = hipMemcpyAsync(dst, d_dst, total * 4, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) return done(fail(RB_EDEVICE, "set values failed: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(RB_EDEVICE, "set values failed: %s", hipGetErrorString(e));
   }
   const KernelSpan spans[1] = {{"k_set_values", 0, 1, ncont}};
-  return done(decoded ? stats_end(ctx, ncont, 0, spans, 1) : stats_end(ctx, 0, 0, spans, 0));
+  return decoded ? stats_end(ctx, ncont, 0, spans, 1) : stats_end(ctx, 0, 0, spans, 0);
 }
 
 int set_lookup(const rbgpu_set *s, int kind, const uint32_t *bitmap, const void *queries, uint64_t n, void *out,
@@ -427,15 +413,12 @@ int set_lookup(const rbgpu_set *s, int kind, const uint32_t *bitmap, const void 
   }
   stats_begin(ctx);
   const size_t qsz = kind == kLookupSelect ? 8 : 4, osz = kind == kLookupContains ? 1 : kind == kLookupRank ? 8 : 4;
+  Scratch w(ctx->pool);
   uint32_t *d_b = nullptr;
   uint8_t *d_q = nullptr, *d_o = nullptr, *d_f = nullptr;
-  auto done = [&](int r) {
-    for (void *p : {(void *)d_b, (void *)d_q, (void *)d_o, (void *)d_f}) ctx->pool.release(p);
-    return r;
-  };
-  if ((bitmap && ctx->pool.alloc((void **)&d_b, n * 4)) || ctx->pool.alloc((void **)&d_q, n * qsz) ||
-      ctx->pool.alloc((void **)&d_o, n * osz) || (kind == kLookupSelect && ctx->pool.alloc((void **)&d_f, n)))
-    return done(fail(RB_ENOMEM, "set lookups of %llu queries", (unsigned long long)n));
+  if ((bitmap && !w.get(d_b, n)) || !w.get(d_q, n * qsz) || !w.get(d_o, n * osz) ||
+      (kind == kLookupSelect && !w.get(d_f, n)))
+    return fail(RB_ENOMEM, "set lookups of %llu queries", (unsigned long long)n);
   hipError_t e = hipMemcpyAsync(d_q, queries, n * qsz, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && bitmap) e = hipMemcpyAsync(d_b, bitmap, n * 4, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], st);
@@ -455,12 +438,12 @@ int set_lookup(const rbgpu_set *s, int kind, const uint32_t *bitmap, const void 
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_o, n * osz, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && kind == kLookupSelect) e = hipMemcpyAsync(found, d_f, n, hipMemcpyDeviceToHost, st);
-  if (e != hipSuccess) return done(fail(RB_EDEVICE, "set lookups failed: %s", hipGetErrorString(e)));
+  if (e != hipSuccess) return fail(RB_EDEVICE, "set lookups failed: %s", hipGetErrorString(e));
   const KernelSpan spans[1] = {{kName[kind], -1, -1, n}};
-  return done(stats_end(ctx, n, 0, spans, 1));
+  return stats_end(ctx, n, 0, spans, 1);
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_values() {}
 void warm_values(hipStream_t st) { k_warm_values<<<1, 64, 0, st>>>(); }
 

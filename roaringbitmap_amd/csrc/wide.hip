@@ -521,11 +521,11 @@ int compact_keyed(rbgpu_ctx *ctx, const uint32_t *d_klist, uint32_t nk, const Wi
     return RB_OK;
   }
   const uint32_t nb = nblk(nk, 256);
+  // the pool buffers go back to the pool when the kernels are queued: the pool only hands them out again to
+  // later work on this stream, which runs after these kernels
+  Scratch w(ctx->pool);
   uint64_t *bk = nullptr, *bks = nullptr;
-  if (ctx->pool.alloc((void **)&bk, (nb + 1) * 8ull) || ctx->pool.alloc((void **)&bks, (nb + 1) * 8ull)) {
-    ctx->pool.release(bk);
-    return fail(RB_ENOMEM, "keyed compaction workspace");
-  }
+  if (!w.get(bk, nb + 1ull) || !w.get(bks, nb + 1ull)) return fail(RB_ENOMEM, "keyed compaction workspace");
   k_wide_keep<<<nb, 256, 0, st>>>(wo.type, nk, bk);
   const uint64_t *in[1] = {bk};
   uint64_t *outp[1] = {bks};
@@ -534,10 +534,6 @@ int compact_keyed(rbgpu_ctx *ctx, const uint32_t *d_klist, uint32_t nk, const Wi
                                    OutView{res->key, res->type, res->card, res->nruns, res->off}, res->begin,
                                    ctx->d_stats);
   LAUNCHCHK();
-  // pool buffers go back to the pool at once: the pool only hands them out again to later work on
-  // this stream, which runs after these kernels
-  ctx->pool.release(bk);
-  ctx->pool.release(bks);
   return RB_OK;
 }
 // after stats_end of a call that ran compact_keyed: its result container count, recorded in the stats
@@ -620,7 +616,6 @@ static int horizontal_order(const rbgpu_set *in, const std::vector<uint32_t> &me
 int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uint32_t> &members_in,
              uint32_t key_lo, uint32_t key_hi, rbgpu_set **out) {
   hipStream_t st = ctx->stream;
-  DevPool &pool = ctx->pool;
   // effective member order: FastAggregation.and(varargs) picks workShyAnd above 10 inputs;
   // naive_and starts from the smallest bitmap (first on ties) and skips it by identity.
   std::vector<uint32_t> members = members_in;
@@ -694,22 +689,13 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
   uint32_t *d_rec = nullptr;
   const uint64_t N1 = std::max<uint64_t>(N, 1);
   const uint64_t tmpw = std::max<uint64_t>(scan_tmp_words(65537), 1);
-  auto alloc_if = [&](bool need, void **p, uint64_t bytes) { return need ? (bool)pool.alloc(p, bytes) : false; };
-  if (pool.alloc((void **)&d_mem, std::max<uint32_t>(M, 1) * 4ull) ||
-      alloc_if(sorted, (void **)&d_bnd, std::max<uint64_t>((uint64_t)M * (nkr + 1), 1) * 8) ||
-      alloc_if(sorted, (void **)&d_Hc, std::max<uint64_t>((uint64_t)nmb * krange, 1) * 4) ||
-      alloc_if(sorted, (void **)&d_H, std::max<uint64_t>((uint64_t)nmb * krange, 1) * 8) ||
-      alloc_if(!dense, (void **)&d_cid2, N1 * 4) || alloc_if(dense, (void **)&d_mbase, std::max<uint32_t>(M, 1) * 8ull) ||
-      pool.alloc((void **)&d_tot, 65537 * 8ull) || pool.alloc((void **)&d_seg, 65537 * 8ull) ||
-      pool.alloc((void **)&d_active, 65537 * 8ull) || pool.alloc((void **)&d_apos, 65537 * 8ull) ||
-      pool.alloc((void **)&d_klist, 65536 * 4ull) || pool.alloc((void **)&d_tmp, tmpw * 8))
+  Scratch w(ctx->pool);
+  if (!w.get(d_mem, M) || (sorted && !w.get(d_bnd, (uint64_t)M * (nkr + 1))) ||
+      (sorted && !w.get(d_Hc, (uint64_t)nmb * krange)) || (sorted && !w.get(d_H, (uint64_t)nmb * krange)) ||
+      (!dense && !w.get(d_cid2, N1)) || (dense && !w.get(d_mbase, M)) || !w.get(d_tot, 65537) ||
+      !w.get(d_seg, 65537) || !w.get(d_active, 65537) || !w.get(d_apos, 65537) || !w.get(d_klist, 65536) ||
+      !w.get(d_tmp, tmpw))
     return fail(RB_ENOMEM, "wide workspace (%llu containers)", (unsigned long long)N);
-  auto release = [&]() {
-    for (void *p : {(void *)d_mem, (void *)d_bnd, (void *)d_Hc, (void *)d_H, (void *)d_cid2, (void *)d_tot,
-                    (void *)d_seg, (void *)d_active, (void *)d_apos, (void *)d_klist, (void *)d_tmp, (void *)d_rec,
-                    (void *)d_mbase})
-      if (p) pool.release(p);
-  };
   if (M) HIPCHK(hipMemcpyAsync(d_mem, members.data(), M * 4ull, hipMemcpyHostToDevice, st));
   const SetView sv = in->view();
   const GroupArgs ga{sv, d_mem, d_bnd, M, MB, KR, nkr, key_lo, key_hi};
@@ -718,11 +704,8 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
   if (horizontal) {
     // the queue order of FastAggregation.horizontal_* over every member key (ties included), then the
     // per-key containers in that order; keys outside the shard are left to k_wide_select
-    int rc = horizontal_order(in, members, h_cid, h_seg);
-    if (rc) {
-      release();
-      return rc;
-    }
+    const int rc = horizontal_order(in, members, h_cid, h_seg);
+    if (rc) return rc;
     if (!h_cid.empty()) HIPCHK(hipMemcpyAsync(d_cid2, h_cid.data(), 4 * h_cid.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_seg, h_seg.data(), 8 * 65537ull, hipMemcpyHostToDevice, st));
   } else if (dense) {
@@ -756,27 +739,17 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
   const uint32_t nk = (and_sem && M == 0) ? 0 : (uint32_t)pin[0];
 
   // ---- per-key reduction into 8 KiB slots
-  rbgpu_set *res = new rbgpu_set;
-  int rc = set_alloc(ctx, res, 1, nk, (uint64_t)std::max<uint32_t>(nk, 1) * kBitmapBytes);
-  if (rc) {
-    delete res;
-    release();
-    return rc;
-  }
+  SetPtr res_owner;
+  int rc = make_set(ctx, 1, nk, (uint64_t)std::max<uint32_t>(nk, 1) * kBitmapBytes, res_owner);
+  if (rc) return rc;
+  rbgpu_set *res = res_owner.get();
   uint8_t *w_type;
   uint32_t *w_card;
   uint16_t *w_nruns;
-  const uint64_t nk1 = std::max<uint32_t>(nk, 1);
-  if (pool.alloc((void **)&w_type, nk1) || pool.alloc((void **)&w_card, nk1 * 4) ||
-      pool.alloc((void **)&w_nruns, nk1 * 2)) {
-    rbgpu_set_free(res);
-    release();
-    return fail(RB_ENOMEM, "wide result workspace");
-  }
+  if (!w.get(w_type, nk) || !w.get(w_card, nk) || !w.get(w_nruns, nk)) return fail(RB_ENOMEM, "wide result workspace");
   WideOut wo{w_type, w_card, w_nruns};
   uint8_t *d_route = nullptr;
-  if (pool.alloc((void **)&d_route, nk1)) d_route = nullptr;
-  if (!d_route) fast_ok = false;
+  if (!w.get(d_route, nk)) fast_ok = false;
   // naive_xor's fast path reads key-major member records (wide_xor.hip)
   XorRecords xr{nullptr, N, XorRecords::kGather, in->mrec, d_mbase, M, key_lo, key_hi};
   if (nk && fast_ok && sem == RB_FAST_XOR) {
@@ -784,7 +757,7 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
       xr.rec = in->krec + (uint64_t)(key_lo - in->dense_lo) * in->nb;
       xr.build = XorRecords::kCached;
     } else {
-      if (pool.alloc((void **)&d_rec, std::max<uint64_t>(N, 1) * 4)) fast_ok = false;
+      if (!w.get(d_rec, N)) fast_ok = false;
       xr.rec = d_rec;
       xr.build = dense ? XorRecords::kTranspose : XorRecords::kGather;
     }
@@ -811,12 +784,7 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
   }
   HIPCHK(hipEventRecord(ctx->ev[2], st));
   // ---- compaction
-  rc = compact_keyed(ctx, d_klist, nk, wo, res);
-  if (rc) {
-    rbgpu_set_free(res);
-    release();
-    return rc;
-  }
+  if ((rc = compact_keyed(ctx, d_klist, nk, wo, res))) return rc;
   // the span covers the Run-list fast path (if any) and the generic kernel for the routed keys
   const bool fp = fast_ok;
   const char *name = sem == RB_FAST_OR ? "k_wide_reduce<FAST_OR>"
@@ -829,22 +797,13 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
                      : sem == RB_HORIZONTAL_XOR ? "k_wide_reduce<HORIZONTAL_XOR>" : "k_wide_reduce<NAIVE_AND>";
   const KernelSpan spans[1] = {{name, 0, 1, nk}};
   // ev[2] -> ev[3]: nothing; stats_end reads ev[1]..ev[2] for kernel 0
-  rc = stats_end(ctx, N, 0, spans, 1);
-  if (!rc) keyed_result_count(ctx, res);
-  pool.release(w_type);
-  pool.release(w_card);
-  pool.release(w_nruns);
-  pool.release(d_route);
-  release();
-  if (rc) {
-    rbgpu_set_free(res);
-    return rc;
-  }
-  *out = res;
+  if ((rc = stats_end(ctx, N, 0, spans, 1))) return rc;
+  keyed_result_count(ctx, res);
+  *out = res_owner.release();
   return RB_OK;
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_wide() {}
 void warm_wide(hipStream_t st) { k_warm_wide<<<1, 64, 0, st>>>(); }
 

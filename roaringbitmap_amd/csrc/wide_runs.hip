@@ -582,7 +582,7 @@ bool launch_wide_runs(int sem, const SetView &s, const uint64_t *mrec, const Cid
   }
 }
 
-// this file's code object, loaded at context creation (warm_code_objects, api.hip)
+// this file's code object, loaded at context creation (rbgpu_open, context.hip)
 __global__ void k_warm_wide_runs() {}
 void warm_wide_runs(hipStream_t st) { k_warm_wide_runs<<<1, 64, 0, st>>>(); }
 

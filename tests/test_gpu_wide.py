@@ -451,7 +451,7 @@ def test_queue_order_ties(ctx, oracle):
 
 
 def test_priorityqueue_or_lazy_roles(ctx, oracle):
-    """FastAggregation.priorityqueue_or on the device (api.hip pq_or, pairwise.hip lazy_or_type): the
+    """FastAggregation.priorityqueue_or on the device (aggregate.hip pq_or, pairwise.hip lazy_or_type): the
     queue's three lazy roles (static lazyor, in-place lazyor, lazyorfromlazyinputs) meet
       key 0  a Run of 1500 two-value runs and Arrays in its gaps: lazyorToRun keeps Runs of 2048..4096
              runs (stored as bitmap words, sized 4r + 4), then more than 4096 -> a lazy Bitmap;
