@@ -434,6 +434,31 @@ int rbgpu_bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *c
  * RunContainer.java:2326-2335).  any_run[n_bitmaps] (may be NULL) receives runOptimize's return value
  * per bitmap (1 when the bitmap holds a Run container afterwards). */
 int rbgpu_set_run_optimize(const rbgpu_set *in, rbgpu_set **out, uint8_t *any_run);
+/* ---- range mutations: RoaringBitmap.add / remove / flip over [start, end) and bitmapOfRange -----
+ * out[i] = op(in[members ? members[i] : i], [start[i], end[i])) — a new set of n bitmaps; `in` is unchanged.  One
+ * range per output bitmap; members may repeat (members NULL: n must be the bitmap count).  The static forms:
+ * RoaringBitmap.add(rb, long, long) (RoaringBitmap.java:298-344), remove(rb, long, long) (:995-1037), flip(bm, long,
+ * long) (:626-664); bitmapOfRange(min, max) (:588-615) is RB_RANGE_ADD on a bitmap without containers.  Container
+ * types are the reference's, so the serialized bytes are (range.hip lists the rules): a key the bitmap does not hold
+ * gets Container.rangeOfOnes (a span of 1 or 2 an Array, else a Run); Array.add / not give an Array up to 4096 values
+ * and a Bitmap above — also when full; Bitmap.add stays a Bitmap, Bitmap.remove / not fall back to an Array at 4096;
+ * Run.add / remove stay a Run of maximal runs whatever their number; Run.not goes through toEfficientContainer; a
+ * container left without members is dropped.  start[i] >= end[i] gives a clone of the bitmap (:300-302, 628-630,
+ * 997-999).  A range outside rangeSanityCheck (:204-213: start > 0xffffffff or end > 2^32) fails the whole call with
+ * RB_EINVAL before any launch, like a bad member index; nothing is created.  The result's arena is sized exactly from a
+ * measuring pass; when it cannot be allocated the call returns RB_ENOMEM before anything is written.
+ * rb_stats: kernel spans k_range_measure and k_range_emit, tasks = result_containers, input_bytes = payload + 16 B of
+ * every source container copied or edited, output_bytes = payload + 16 B per result container. */
+enum rb_range_op { RB_RANGE_ADD = 0, RB_RANGE_REMOVE = 1, RB_RANGE_FLIP = 2 };
+int rbgpu_set_range_op(rbgpu_ctx *ctx, int op, const rbgpu_set *in, const uint32_t *members, const uint64_t *start,
+                       const uint64_t *end, uint32_t n, rbgpu_set **out);
+/* The state of in[members[i]] after x.add(start, end) / x.remove(start, end) / x.flip(start, end) in place
+ * (RoaringBitmap.java:1181-1208, 2656-2711, 1893-1925).  The same sets and container types as the static forms with
+ * one exception: the static add writes rangeOfOnes(0, 65536), a full Run, at every key strictly inside the span
+ * whatever the bitmap held there (:332-335), while x.add calls iadd on the containers it finds (:1199-1202), so an
+ * Array or Bitmap strictly inside the span becomes a full Bitmap.  Inputs stay unchanged (results are new sets). */
+int rbgpu_set_range_op_inplace(rbgpu_ctx *ctx, int op, const rbgpu_set *in, const uint32_t *members,
+                               const uint64_t *start, const uint64_t *end, uint32_t n, rbgpu_set **out);
 /* RoaringBitmap.clone of bitmaps [first, first+count) into a new set (device copy). */
 int rbgpu_set_extract(const rbgpu_set *set, uint32_t first, uint32_t count, rbgpu_set **out);
 /* The per-set metadata the wide kernels derive on a set's first use and keep with it (sets are

@@ -24,6 +24,7 @@ RB64_BITMAP, RB64_NAVIGABLE = 0, 1  # rbgpu.h rb64_flavor: Roaring64Bitmap / Roa
 EMPTY_BITMAP = 0xFFFFFFFF           # RB_EMPTY_BITMAP pair index
 WL_FILTER_POSTING, WL_WIDE_DENSE, WL_WIDE_MIXED, WL_WIDE_RUNS = range(4)
 BSI_EQ, BSI_NEQ, BSI_LE, BSI_LT, BSI_GE, BSI_GT, BSI_RANGE = range(7)  # BitmapSliceIndex.Operation
+RANGE_ADD, RANGE_REMOVE, RANGE_FLIP = range(3)  # rb_range_op
 BUILD_RUN_OPTIMIZE = 1  # rb_build_flags
 BUILD_TILE = 1024       # RB_BUILD_TILE: elements per block of the value build's container discovery
 
@@ -138,6 +139,10 @@ SIGNATURES = {
     "rbgpu_set_device_view": (C.c_int, [_P, C.POINTER(RbDeviceView)]),
     "rbgpu_pairwise_inplace": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_uint32, C.POINTER(_P)]),
     "rbgpu_set_run_optimize": (C.c_int, [_P, C.POINTER(_P), C.c_void_p]),
+    # range mutations: member / start / end arrays as void* (plain host addresses)
+    "rbgpu_set_range_op": (C.c_int, [_P, C.c_int, _P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(_P)]),
+    "rbgpu_set_range_op_inplace": (C.c_int, [_P, C.c_int, _P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                             C.POINTER(_P)]),
     "rbgpu_set_setup_stats": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     "rbgpu_set_setup_parts": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     "rbgpu_set64_from_portable": (C.c_int, [_P, C.POINTER(C.c_char_p), _U64P, C.c_uint32, C.POINTER(_P)]),

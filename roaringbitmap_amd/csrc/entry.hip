@@ -143,6 +143,40 @@ int rbgpu_generate_bsi_keys(rbgpu_ctx *ctx, uint32_t nslices, uint64_t nrows, ui
   return generate_bsi(ctx, nslices, nrows, seed, key_lo, key_hi, out);
 }
 
+// ---------------------------------------------------------------- range mutations (range.hip)
+static int range_op_call(rbgpu_ctx *ctx, int op, bool inplace, const rbgpu_set *in, const uint32_t *members,
+                         const uint64_t *start, const uint64_t *end, uint32_t n, rbgpu_set **out) {
+  if (!out) return fail(RB_EINVAL, "null out");
+  *out = nullptr; // before anything can fail: no path leaves the caller's word as it was
+  SETTLE(in);
+  int rc = check_ctx(ctx);
+  if (rc) return rc;
+  if (!in || in->ctx != ctx) return fail(RB_EINVAL, "bad input set");
+  if (op < RB_RANGE_ADD || op > RB_RANGE_FLIP) return fail(RB_EINVAL, "unknown range op %d", op);
+  if (n && (!start || !end)) return fail(RB_EINVAL, "null range arrays");
+  if (!members && n != in->nb) return fail(RB_EINVAL, "without a member list n must be the bitmap count");
+  for (uint32_t i = 0; i < n; ++i) {
+    if (members && members[i] >= in->nb)
+      return fail(RB_EINVAL, "members[%u] = %u: the set holds %u bitmaps", i, members[i], in->nb);
+    // rangeSanityCheck (RoaringBitmap.java:204-213)
+    if (start[i] > 0xFFFFFFFFull)
+      return fail(RB_EINVAL, "rangeStart=%llu should be in [0, 0xffffffff]", (unsigned long long)start[i]);
+    if (end[i] > (1ull << 32))
+      return fail(RB_EINVAL, "rangeEnd=%llu should be in [0, 0xffffffff + 1]", (unsigned long long)end[i]);
+  }
+  return range_op(ctx, op, inplace, in, members, start, end, n, out);
+}
+
+int rbgpu_set_range_op(rbgpu_ctx *ctx, int op, const rbgpu_set *in, const uint32_t *members, const uint64_t *start,
+                       const uint64_t *end, uint32_t n, rbgpu_set **out) {
+  return range_op_call(ctx, op, false, in, members, start, end, n, out);
+}
+
+int rbgpu_set_range_op_inplace(rbgpu_ctx *ctx, int op, const rbgpu_set *in, const uint32_t *members,
+                               const uint64_t *start, const uint64_t *end, uint32_t n, rbgpu_set **out) {
+  return range_op_call(ctx, op, true, in, members, start, end, n, out);
+}
+
 // ---------------------------------------------------------------- generator
 int rbgpu_generate(rbgpu_ctx *ctx, int workload, uint32_t n, uint64_t seed, rbgpu_set **a, rbgpu_set **b) {
   int rc = check_ctx(ctx);

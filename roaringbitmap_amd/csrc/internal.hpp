@@ -435,6 +435,10 @@ int build_set_values(rbgpu_ctx *ctx, const uint32_t *d_values, const uint64_t *o
                      rbgpu_set **out);
 int build_bsi_pairs(rbgpu_ctx *ctx, const uint32_t *d_cols, const uint64_t *d_vals, uint64_t n, uint32_t flags,
                     rbgpu_set **out, uint64_t *min_value, uint64_t *max_value);
+// range.hip: out[i] = in[members ? members[i] : i] with [start[i], end[i]) added / removed / flipped (rb_range_op;
+// host arrays, checked by the caller); inplace: the rules of x.add / x.remove / x.flip(range)
+int range_op(rbgpu_ctx *ctx, int op, bool inplace, const rbgpu_set *in, const uint32_t *members, const uint64_t *start,
+             const uint64_t *end, uint32_t n, rbgpu_set **out);
 // set.hip: the containers of bitmap 0 of `s` with keys in [key_lo, key_hi), as a new one-bitmap set
 int set_key_subset(const rbgpu_set *s, uint32_t key_lo, uint32_t key_hi, rbgpu_set **out);
 int set_gather(const rbgpu_set *s, const uint32_t *idx, uint32_t n, rbgpu_set **out);

@@ -24,6 +24,7 @@ void warm_build(hipStream_t st);
 void warm_codec(hipStream_t st);
 void warm_generate(hipStream_t st);
 void warm_pairwise(hipStream_t st);
+void warm_range(hipStream_t st);
 void warm_scan(hipStream_t st);
 void warm_setops(hipStream_t st);
 void warm_values(hipStream_t st);

@@ -549,6 +549,29 @@ class Context:
         L.check(L.lib().rbgpu_pairwise(self.h, op, a.h, b.h, ap, bp, n, C.byref(out)))
         return DeviceSet(self, out.value)
 
+    def range_op(self, op: int, s: DeviceSet, start, end, members=None, inplace: bool = False) -> DeviceSet:
+        """RoaringBitmap.add / remove / flip over [start, end) (op: RANGE_ADD / RANGE_REMOVE / RANGE_FLIP) for a
+        batch: result i is bitmap members[i] of `s` (members None: bitmap i) with [start[i], end[i]) applied, a
+        new set; `s` is unchanged (rbgpu_set_range_op).  start / end: one value each per result, or scalars for
+        all.  inplace: the container types of x.add / x.remove / x.flip(range) (rbgpu_set_range_op_inplace; they
+        differ from the static forms only for add, at keys strictly inside the span).  A range outside
+        rangeSanityCheck (start in [0, 2^32), end in [0, 2^32]) raises ValueError and creates nothing."""
+        mi, mp = _idx_addr(members)
+        n = len(mi) if mi is not None else len(s)
+        bounds = []
+        for name, v, top in (("rangeStart", start, 0xFFFFFFFF), ("rangeEnd", end, 1 << 32)):
+            v = [int(x) for x in (np.ravel(v).tolist() if np.ndim(v) else [v] * n)]
+            if len(v) != n:
+                raise ValueError(f"{name}: {len(v)} values for {n} bitmaps")
+            bad = next((x for x in v if x < 0 or x > top), None)
+            if bad is not None:  # rangeSanityCheck (RoaringBitmap.java:204-213)
+                raise L.InvalidArgument(L.RB_EINVAL, f"{name}={bad} should be in [0, {top:#x}]")
+            bounds.append(np.asarray(v, dtype=np.uint64))
+        fn = L.lib().rbgpu_set_range_op_inplace if inplace else L.lib().rbgpu_set_range_op
+        out = C.c_void_p()
+        L.check(fn(self.h, op, s.h, mp, bounds[0].ctypes.data, bounds[1].ctypes.data, n, C.byref(out)))
+        return DeviceSet(self, out.value)
+
     # ---- 64-bit bitmaps (longlong/)
     def upload_portable64(self, blobs: Sequence[bytes]) -> "DeviceSet64":
         """Roaring64NavigableMap.deserializePortable per blob (rbgpu_set64_from_portable)."""

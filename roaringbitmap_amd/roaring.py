@@ -10,6 +10,11 @@ MI355X through librbgpu (no CPU fallback).
   RoaringBitmap.*Cardinality(x1, x2)           RoaringBitmap.java:413, 916, 931, 944
   RoaringBitmap.or_(*bitmaps)                   RoaringBitmap.java:844 -> FastAggregation.or
   x.runOptimize()                               RoaringBitmap.java:2764
+  RoaringBitmap.add/remove/flip(rb, start, end) static, RoaringBitmap.java:298, 995, 626
+  x.add/remove/flip(start, end)                 in place, RoaringBitmap.java:1181, 2656, 1893
+  RoaringBitmap.bitmapOfRange(min, max)         RoaringBitmap.java:588
+  x.contains(minimum, supremum)                 RoaringBitmap.java:1709
+  x.intersects(minimum, supremum)               RoaringBitmap.java:1234
   FastAggregation.and_/or_/xor(*bitmaps)        FastAggregation.java:37, 602, 772
   FastAggregation.naive_and/workShyAnd/...      FastAggregation.java:328, 356, 477, 541, 576
   ParallelAggregation.or_/xor(*bitmaps)         ParallelAggregation.java:161, 182
@@ -47,6 +52,35 @@ class _StaticOrInPlace:
         if obj is None:
             return lambda x1, x2: cls._pair(op, x1, x2)
         return lambda x2: obj._inplace(op, x2)
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+class _StaticOrInPlaceRange:
+    """RoaringBitmap.add / remove / flip(rb, rangeStart, rangeEnd) (static, a new bitmap; rb is unchanged) when
+    looked up on the class, x.add / remove / flip(rangeStart, rangeEnd) (in place, returns None) when looked up on
+    an instance.  The overload is decided by class-vs-instance and by the argument types; any other call shape is
+    a TypeError (there is no single-value form here)."""
+
+    def __init__(self, op: int, name: str):
+        self.op, self.name = op, name
+
+    def __get__(self, obj, cls):
+        op, name = self.op, self.name
+        if obj is None:
+            def static(rb, rangeStart, rangeEnd):
+                if not (isinstance(rb, RoaringBitmap) and _is_int(rangeStart) and _is_int(rangeEnd)):
+                    raise TypeError(f"RoaringBitmap.{name}(rb, rangeStart, rangeEnd)")
+                return cls(default_context().range_op(op, rb._set, rangeStart, rangeEnd))
+            return static
+
+        def inplace(rangeStart, rangeEnd):
+            if not (_is_int(rangeStart) and _is_int(rangeEnd)):
+                raise TypeError(f"x.{name}(rangeStart, rangeEnd)")
+            obj._set = default_context().range_op(op, obj._set, rangeStart, rangeEnd, inplace=True)
+        return inplace
 
 
 class RoaringBitmap:
@@ -90,8 +124,13 @@ class RoaringBitmap:
         return self._set.to_arrays()[0]
 
     # ---- the value side: contains / rank / select (RoaringBitmap.java:1693, 2574, 2622, 2820), on the device
-    def contains(self, x):
-        """contains(int x); an array of values gives an array of bools (one batched call)."""
+    def contains(self, x, supremum=None):
+        """contains(int x); an array of values gives an array of bools (one batched call).  contains(long minimum,
+        long supremum) (:1709): whether every value of [minimum, supremum) is a member — rangeCardinality over the
+        range against its length; an empty range is not contained; a range outside rangeSanityCheck: ValueError."""
+        if supremum is not None:
+            minimum, supremum = self._sane_range(x, supremum)
+            return supremum > minimum and self.rangeCardinality(minimum, supremum) == supremum - minimum
         if np.ndim(x) == 0:
             return bool(self._set.contains([int(x) & 0xFFFFFFFF])[0])
         return self._set.contains(np.asarray(x).astype(np.uint32))
@@ -145,6 +184,32 @@ class RoaringBitmap:
             return int(self._set.rank([end - 1])[0])
         r = self._set.rank([end - 1, start - 1])
         return int(r[0]) - int(r[1])
+
+    @staticmethod
+    def _sane_range(minimum, supremum):
+        """rangeSanityCheck (:204-213): ValueError where the reference throws IllegalArgumentException."""
+        minimum, supremum = int(minimum), int(supremum)
+        if minimum < 0 or minimum > 0xFFFFFFFF:
+            raise ValueError(f"rangeStart={minimum} should be in [0, 0xffffffff]")
+        if supremum < 0 or supremum > 1 << 32:
+            raise ValueError(f"rangeEnd={supremum} should be in [0, 0xffffffff + 1]")
+        return minimum, supremum
+
+    def intersects(self, minimum: int, supremum: int) -> bool:
+        """intersects(long minimum, long supremum) (:1234): whether a member lies in [minimum, supremum)."""
+        minimum, supremum = self._sane_range(minimum, supremum)
+        return supremum > minimum and self.rangeCardinality(minimum, supremum) > 0
+
+    # ---- range mutations (RoaringBitmap.java:298, 995, 626 static; :1181, 2656, 1893 in place), on the device
+    add = _StaticOrInPlaceRange(L.RANGE_ADD, "add")
+    remove = _StaticOrInPlaceRange(L.RANGE_REMOVE, "remove")
+    flip = _StaticOrInPlaceRange(L.RANGE_FLIP, "flip")
+
+    @staticmethod
+    def bitmapOfRange(min: int, max: int) -> "RoaringBitmap":  # noqa: A002 (the reference's parameter names)
+        """bitmapOfRange(long min, long max) (:588-615): [min, max) as rangeOfOnes containers — add(min, max) on a
+        bitmap without containers."""
+        return RoaringBitmap.add(RoaringBitmap(), min, max)
 
     def runOptimize(self) -> bool:
         """RoaringBitmap.runOptimize (RoaringBitmap.java:2764-2775) on the device: each container takes
