@@ -2,11 +2,6 @@
 #pragma once
 #include "common.hpp"
 
-// workShyAnd's run fast path reads the set's SoA metadata directly instead of packed per-set records (mrec):
-// no setup pass on a fresh set (wide_runs.hip AndRec)
-#ifndef RBG_AND_SOA
-#define RBG_AND_SOA 1 // study builds: 0 packs the set's records (mrec) on its first workShyAnd and reads those
-#endif
 namespace rbg {
 
 // ---- scan.hip
@@ -172,14 +167,15 @@ struct SmallPairArgs {
                                // input bytes | card << 32 — sc1 stores the compaction polls for (kSlotUnset
                                // between calls: the context's buffer, reset by the compaction)
   uint64_t *pcard;             // [np] result cardinality per pair, or null
-  uint64_t *ctr;               // [0] started blocks (agent atomic; zero between calls: the last block resets it)
+  uint64_t *ctr;               // [0] the context's block counter word: nothing here counts on it, the compaction zeroes it
   int lazy;                    // 0, or the priorityqueue_or role of an OR call (TaskMeta::lazy)
   int inplace;                 // in-place x1.op(x2) (PairArgs::inplace)
   int keep_empty;              // TaskMeta::keep_empty
-  // the compaction's: E slots, nblocks blocks, slot -> result position scratch (used above
+  // the compaction's: E slots (`reserved`: unused, it keeps the argument block as the kernel is compiled for it),
+  // slot -> result position scratch (used above
   // kSmallXposLds slots), result SoA (key null: cardinality only), result CSR or null, host-visible
   // words: [0] result containers, [1..4] the summed counters
-  uint32_t E, nblocks;
+  uint32_t E, reserved;
   uint32_t *xpos;
   uint64_t *rbegin, *hout; // hout: host-visible result words [0..4], and [5] = seq once they are written
   uint64_t seq;
@@ -242,13 +238,14 @@ struct XorRecords {
 // member m's container at key k is mbase[m] - bias + k (a dense set: mbase = the set's begin, bias = key_lo)
 // pairs: every mbase[m] - bias + key_lo is even (two containers per lane, 128-key tiles)
 void launch_records_direct(const SetView &s, const uint64_t *mbase, uint64_t bias, uint32_t M, uint32_t key_lo,
-                           uint32_t key_hi, uint32_t *rec, hipStream_t st, bool pairs = false, bool quads = false);
+                           uint32_t key_hi, uint32_t *rec, hipStream_t st, bool pairs = false);
 void launch_records_transpose(const uint64_t *mrec, const uint64_t *mbase, uint64_t bias, uint32_t M, uint32_t key_lo,
                               uint32_t key_hi, uint32_t *rec, hipStream_t st);
 void launch_wide_runs_xor(const SetView &s, const uint32_t *cid, const uint64_t *seg, const uint32_t *klist,
                           uint32_t nk, uint8_t *out, const WideOut &wo, uint8_t *route, uint64_t *stats,
                           const XorRecords &xr, hipStream_t st);
-// mrec: the set's packed records (workShyAnd's one-load metadata)
+// mrec: the set's packed records (workShyAnd's one-load metadata) when it already has them; null: workShyAnd
+// reads the set's SoA metadata directly — no setup pass on a fresh set (wide_runs.hip AndRec)
 bool launch_wide_runs(int sem, const SetView &s, const uint64_t *mrec, const CidMap &cm, const uint64_t *seg,
                       const uint32_t *klist, uint32_t nk, uint8_t *out, const WideOut &wo, uint8_t *route,
                       uint64_t *stats, const XorRecords &xr, hipStream_t st);

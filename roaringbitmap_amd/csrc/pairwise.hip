@@ -21,19 +21,6 @@ namespace rbg {
 
 constexpr int kPairThreads = 256;
 
-#ifndef RBG_SMALL_STUDY
-#define RBG_SMALL_STUDY 0 // study builds: per-block phase times (s_memrealtime) into g_small_study (rbgpu_internal_small_study)
-#endif
-#if RBG_SMALL_STUDY
-constexpr int kStudyWords = 32; // per block: t0, align, 4 wave ends, 4 key counts, done, compact end, pair, sub, nu, last;
-                                // 16 + 4 w: wave w's slowest key (ticks, result | operand types, operand cards, merge phases)
-__device__ uint64_t g_small_study[8192 * kStudyWords];
-__device__ uint64_t g_merge_ts[8192 * 4][8]; // per wave: merge_run's phase stamps of its last merge
-#define RBG_MT(i) if (lane == 0) g_merge_ts[min(blockIdx.x, 8191u) * 4 + (threadIdx.x >> 6)][i] = __builtin_amdgcn_s_memrealtime()
-#else
-#define RBG_MT(i)
-#endif
-
 __device__ __forceinline__ bool keeps_a_only(int op) { return op != RB_AND; }
 __device__ __forceinline__ bool keeps_b_only(int op) { return op == RB_OR || op == RB_XOR || is_lazy_op(op); }
 
@@ -108,9 +95,6 @@ __device__ __forceinline__ WalkMeta pick_meta(const WalkMeta (&m)[kWalkRegs], ui
 // and once, after a wave scan of the counts, to store them.  With ca + cb <= kMergeMax the result is an
 // Array (ArrayContainer.or / xor merge below DEFAULT_MAX_SIZE; and / andNot are subsets of A), the type
 // the register path gives these pairs.  Used by the small-batch kernel (k_pair_small).
-#ifndef RBG_SMALL_MERGE
-#define RBG_SMALL_MERGE 1 // study builds: 0 sends small-batch Array pairs through the register path
-#endif
 constexpr uint32_t kMergeMax = 4088; // ca + cb: A at 0, B 16-B aligned after it, both in 8 KiB
 template <int OP>
 __device__ __forceinline__ bool merge_keep(bool from_a, bool matched) {
@@ -209,9 +193,6 @@ __device__ __forceinline__ uint32_t merge_small_side(const uint16_t *A, uint32_t
 // but two running counts, so their LDS reads pipeline.  Returns the result count; kLopsidedNo when the bitmaps
 // do not fit beside the staged arrays (the caller walks).
 constexpr uint32_t kLopsidedNo = 0xFFFFFFFFu;
-#ifndef RBG_LOPSIDED
-#define RBG_LOPSIDED 1 // lopsided pairs off the walk, counted before the store sweep (0: the walk; profiles/r06/small/early)
-#endif
 template <int OP, bool STORE, class Pub = NoPub>
 __device__ __forceinline__ uint32_t merge_lopsided(uint16_t *A, uint32_t ca, uint32_t boff, uint32_t cb, uint16_t *out,
                                                    int lane, const Pub &pub = Pub()) {
@@ -280,12 +261,12 @@ __device__ __forceinline__ uint32_t merge_run(uint32_t *s, uint32_t ca, uint32_t
     wave_lds_sync(); // the next task restages the scratch
     return tot;
   }
-  // one side of <= 64 values into the other: insertions / deletions (merge_lopsided)
-  if (RBG_LOPSIDED && (((OP == RB_OR || OP == RB_XOR) && min(ca, cb) <= 64u) || (OP == RB_ANDNOT && cb <= 64u))) {
+  // one side of <= 64 values into the other: insertions / deletions (merge_lopsided), off the walk and counted
+  // before the store sweep (against the walk: profiles/r06/small/early)
+  if (((OP == RB_OR || OP == RB_XOR) && min(ca, cb) <= 64u) || (OP == RB_ANDNOT && cb <= 64u)) {
     const uint32_t tot = merge_lopsided<OP, STORE>(A, ca, boff, cb, out, lane, pub);
     if (tot != kLopsidedNo) return tot;
   }
-  RBG_MT(0);
   const uint32_t d0 = ((uint32_t)lane * n) >> 6, d1 = ((uint32_t)(lane + 1) * n) >> 6;
   // merge path: the number of A values among the first d0 merged values (A first on ties)
   uint32_t lo = d0 > cb ? d0 - cb : 0u, hi = min(d0, ca);
@@ -298,11 +279,9 @@ __device__ __forceinline__ uint32_t merge_run(uint32_t *s, uint32_t ca, uint32_t
   // and B, else a counting walk and a storing walk
   const uint32_t sbase = (boff + cb + 7u) & ~7u;
   const bool staged = STORE && sbase + n <= 4096u; // wave-uniform
-  RBG_MT(1);
   uint32_t cnt;
   if (staged) cnt = merge_walk<OP, false, true>(A, ca, boff, cb, lo, d0 - lo, d1 - d0, nullptr, A + sbase + d0);
   else cnt = merge_walk<OP, false, false>(A, ca, boff, cb, lo, d0 - lo, d1 - d0, nullptr, nullptr);
-  RBG_MT(2);
   const uint32_t incl = wave_scan_u32(cnt, lane), tot = readlane(incl, 63);
   pub(tot);
   if (STORE && tot) { // out: a 16-B aligned slot
@@ -322,11 +301,9 @@ __device__ __forceinline__ uint32_t merge_run(uint32_t *s, uint32_t ca, uint32_t
           if (k + (uint32_t)u < cnt) o16[k + u] = v[u];
       }
       wave_lds_sync();
-      RBG_MT(3);
       const uint4 *a4 = reinterpret_cast<const uint4 *>(A);
       uint4 *o4 = reinterpret_cast<uint4 *>(out);
       for (uint32_t c = (uint32_t)lane; 16u * c < 2u * tot; c += 64u) o4[c] = a4[c];
-      RBG_MT(4);
     } else {
       merge_walk<OP, true, false>(A, ca, boff, cb, lo, d0 - lo, d1 - d0, o, nullptr);
     }
@@ -340,28 +317,14 @@ __device__ __forceinline__ uint32_t merge_run(uint32_t *s, uint32_t ca, uint32_t
 // (OR / XOR of two Arrays through merge_run in the light (copy + filter) kernel instead of the heavy
 // register path measured slower:
 // config 2 OR 12.84 -> 14.09 ms, XOR 10.59 -> 12.85 — the light kernel, already the L2-bound one, became
-// the long pole; an LDS-image form of the same tasks 15.8 / 14.2 ms.  profiles/r05/merge.)
+// the long pole; an LDS-image form of the same tasks 15.8 / 14.2 ms.  profiles/r05/merge.  Round 6: an OR
+// into a Bitmap operand of more than 4096 values, whose LR type is known before the OR, done there row by
+// row was slower too: config 2 OR 13.12 vs 12.36 ms)
 __device__ __forceinline__ bool light_task(int op, int ta, int tb) {
   if (ta < 0 || tb < 0) return true;
   if (op == RB_AND) return ta == kArray || tb == kArray;
   if (op == RB_ANDNOT) return ta == kArray;
   return false;
-}
-// Round 6: an OR with a Bitmap operand of more than 4096 values (canonical, no lazy marks) holds all of that
-// operand's values, so its LR type (BitmapContainer.or(Array / Bitmap / Run), BitmapContainer.java:1073-1110;
-// RunContainer.or(Bitmap)) is known before the OR: a Bitmap, or the full Run when c = 65536 (and a Bitmap even
-// then for BitmapContainer.ior(ArrayContainer), :749-766).  Such a task needs no register image and no
-// emission loops: the copy + filter kernel ORs the staged other operand into it row by row (kBits), at that
-// kernel's occupancy.  Only the plain OR: the lazy roles keep the register path's lazy types.
-#ifndef RBG_OR_BITS
-#define RBG_OR_BITS 0 // study builds: 1 sends them to the copy + filter kernel (slower: config 2 OR 13.12 vs 12.36 ms)
-#endif
-__device__ __forceinline__ bool big_bitmap(int t, uint32_t c) {
-  return t == kBitmap && !(c & kCardMarks) && c > (uint32_t)kMaxArray;
-}
-__device__ __forceinline__ bool bits_task(int op, int ta, uint32_t ca, int tb, uint32_t cb) {
-  return RBG_OR_BITS && op == RB_OR && (uint32_t)ta <= 2u && (uint32_t)tb <= 2u &&
-         (big_bitmap(ta, ca) || big_bitmap(tb, cb));
 }
 
 // Striped accounting (stats word w, stripe = block mod kStripes) of N counters: one atomic per block
@@ -497,7 +460,7 @@ __device__ __forceinline__ void pair_walk(const PairArgs &a, uint64_t sg, PairCo
   // one result slot from the two sides' container metadata (ta / tb < 0: no container on that side)
   auto slot_v = [&](int ta, uint32_t ca, uint32_t ra, uint64_t oa, int tb, uint32_t cb, uint32_t rb, uint64_t ob,
                     uint16_t key, bool big, uint64_t bytes) {
-    const bool lt = light_task(a.op, ta, tb) || bits_task(a.op, ta, ca, tb, cb);
+    const bool lt = light_task(a.op, ta, tb);
     if (!EMIT) {
       uint64_t b = 0;
       if (ta >= 0) b += alg_bytes(ta, ca, ra) + 16;
@@ -672,10 +635,8 @@ constexpr uint32_t kEmitStage = 640; // records (25 KiB); a block with more stor
 // cnt: the segments' counts, bs: the exclusive scans of the block totals (bs.x[blockIdx]); every
 // segment's task offset is also stored in task_begin[p] (task_begin[nseg] = the total) for the
 // compaction.
-#ifndef RBG_EMIT_WAVES
-#define RBG_EMIT_WAVES 1 // study builds: waves per SIMD the emit is compiled for (1: no bound; 119 VGPRs = 4 waves)
-#endif
-__global__ __launch_bounds__(kPairThreads, RBG_EMIT_WAVES) void k_pair_emit(PairArgs a, const uint64_t *cnt, PairCountArrays bs,
+constexpr int kEmitWaves = 1; // waves per SIMD the emit is compiled for (1: no bound; 119 VGPRs = 4 waves)
+__global__ __launch_bounds__(kPairThreads, kEmitWaves) void k_pair_emit(PairArgs a, const uint64_t *cnt, PairCountArrays bs,
                                                             uint64_t small_base, TaskRec *light, TaskRec *heavy,
                                                             TaskMeta tm, uint64_t *task_begin, const uint64_t *tot,
                                                             uint64_t cap, unsigned long long *zero_q) {
@@ -777,44 +738,25 @@ __device__ __forceinline__ RecU load_rec(const TaskRec *r) {
 //           the left; ArrayContainer.and/andNot :184-271, BitmapContainer.and(Array) :162-172,
 //           RunContainer.and(Array) :305-336): P = F, Q = the other operand X, staged in LDS;
 //   kHeavy  everything else: P = A, Q = B as 65536-bit register bitmaps.
-#ifndef RBG_HEAVY_MERGE
-#define RBG_HEAVY_MERGE 0 // study builds: 1 merges OR / XOR of two small Arrays here (slower: DESIGN.md §7 r06)
-#endif
-#ifndef RBG_BAL_EMIT
-#define RBG_BAL_EMIT 0 // study builds: 1 emits register-path Array / Run results by per-lane cursor walks (slower)
-#endif
 constexpr int kLightWaves = 4; // waves per SIMD of the copy + filter kernel (128 VGPRs)
-#ifndef RBG_HEAVY_WAVES
-#define RBG_HEAVY_WAVES 2
-#endif
-constexpr int kHeavyWaves = RBG_HEAVY_WAVES; // waves per SIMD the register-path kernel is allocated for
-#ifndef RBG_STUDY
-#define RBG_STUDY 0 // study builds: per-phase s_memtime totals of a few light / heavy waves (printf)
-#endif
-enum { kCopy = 0, kFilter = 1, kHeavy = 2, kBits = 3 };
+constexpr int kHeavyWaves = 2; // waves per SIMD the register-path kernel is allocated for
+enum { kCopy = 0, kFilter = 1, kHeavy = 2 };
 struct Task {
   int kind;
   bool bigp, bigq;       // payload exceeds 8 KiB (Run with > 2047 runs): direct path from global
-  bool p_is_a;           // P is A's container (kBits: the inplace Bitmap.ior(Array) rule reads it)
   const uint8_t *pp, *pq;
   uint32_t pbytes, qbytes;
   int tp, tq;            // container types of P and Q
   uint32_t cp, cq, rp, rq;
 };
-// LIGHT: the copy + filter kernel's view, where a matched OR pair is a kBits task (bits_task: the walk sends
-// no other matched OR pair there); P is then the large Bitmap (A's when both qualify)
-template <int OP, bool LIGHT>
+template <int OP>
 __device__ __forceinline__ Task decode_task(const RecU &r, const uint8_t *pay_a, const uint8_t *pay_b) {
   Task T;
   const uint32_t ta = desc_type(r.da), tb = desc_type(r.db);
   const uint32_t ca = desc_card(r.da), cb = desc_card(r.db);
-  const bool bits = LIGHT && RBG_OR_BITS && OP == RB_OR && ta != kAbsent && tb != kAbsent;
-  const bool p_is_a = bits ? big_bitmap((int)ta, ca)
-                           : ta != kAbsent && !(light_task(OP, (int)ta, (int)tb) && tb == kArray &&
-                                                (ta != kArray || (OP != RB_ANDNOT && cb < ca)));
-  T.p_is_a = p_is_a;
+  const bool p_is_a = ta != kAbsent && !(light_task(OP, (int)ta, (int)tb) && tb == kArray &&
+                                         (ta != kArray || (OP != RB_ANDNOT && cb < ca)));
   if (ta == kAbsent || tb == kAbsent) T.kind = kCopy;
-  else if (bits) T.kind = kBits;
   else T.kind = light_task(OP, (int)ta, (int)tb) ? kFilter : kHeavy;
   // kFilter: F is the Array (ANDNOT: always A; AND of two Arrays: the smaller, A on ties)
   T.pp = p_is_a ? pay_a + r.pa : pay_b + r.pb;
@@ -1042,9 +984,6 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
   __shared__ __attribute__((aligned(16))) uint32_t lds[4][2048];
   __shared__ __attribute__((aligned(16))) uint16_t stage[ROLE == kRoleLight ? 4 : 1][kStageVals];
   __shared__ uint4 tbuf[ROLE == kRoleLight ? 4 : 1][32]; // per-wave half-row transpose (filter_rows_linear)
-  // register path: a second 8 KiB per wave for the balanced Array / Run emission (wave.hpp emit_container_bal)
-  __shared__ __attribute__((aligned(16))) uint32_t estage[ROLE == kRoleHeavy && RBG_BAL_EMIT ? 4 : 1]
-                                                        [ROLE == kRoleHeavy && RBG_BAL_EMIT ? 2048 : 4];
   const int lane = lane_id();
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // static schedule (queue == nullptr): wave w takes tasks w, w + stride, ...; dynamic: chunks of
@@ -1064,17 +1003,8 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
   uint32_t *s = lds[wv];
   uint16_t *ob = stage[ROLE == kRoleLight ? wv : 0];
   RecU cur = load_rec(recs + g);
-  Task tc = decode_task<OP, ROLE == kRoleLight>(cur, pay_a, pay_b);
+  Task tc = decode_task<OP>(cur, pay_a, pay_b);
   uint4 pq[8], qq[8];
-#if RBG_STUDY
-  uint64_t lt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, lt0 = 0, lt1 = 0, lt2 = 0; // decode, stage B/A/R, copy, filter, iteration, tasks
-  uint64_t lt_wait = 0; // heavy: cycles waiting for the task's payload loads (an explicit vmcnt(0) at its start)
-#define RBG_LT(x) if (ROLE == kRoleLight) { x; }
-#define RBG_HT(x) if (ROLE == kRoleHeavy) { x; }
-#else
-#define RBG_LT(x)
-#define RBG_HT(x)
-#endif
   // Q before P, the order the loop issues them in: the waits the compiler counts for the loop's first loads
   // take the smaller of the two orders, and P last here made each of them a full drain
   if (tc.kind == kCopy || tc.bigq) load_chunks(qq, tc.pp, 16, lane);
@@ -1092,12 +1022,8 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       }
     }
     const bool has_next = gn < n;
-    RBG_LT(lt0 = __builtin_amdgcn_s_memtime());
-    RBG_HT(lt0 = __builtin_amdgcn_s_memtime());
     const RecU nx = load_rec(recs + (has_next ? gn : g));
-    const Task tn = decode_task<OP, ROLE == kRoleLight>(nx, pay_a, pay_b);
-    RBG_LT(lt1 = __builtin_amdgcn_s_memtime(); lt_acc[0] += lt1 - lt0);
-    RBG_HT(lt1 = __builtin_amdgcn_s_memtime(); lt_acc[0] += lt1 - lt0);
+    const Task tn = decode_task<OP>(nx, pay_a, pay_b);
     int ty = kEmpty, c = 0;
     uint32_t nr = 0, cw = 0xFFFFFFFFu; // cw: the card word to store when it is not c (lazy marks)
     uint8_t *dst = out + cur.out;
@@ -1117,34 +1043,9 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
         load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
       }
     }
-    if (ROLE == kRoleHeavy && RBG_HEAVY_MERGE && !done && (OP == RB_OR || OP == RB_XOR) && !tm.lazy &&
-        tc.tp == kArray && tc.tq == kArray && tc.cp + tc.cq <= kMergeMax) {
-      // ---- Array OR / XOR Array as a merge (merge_run, the small-batch kernel's): the result is an Array
-      //      (c <= ca + cb <= 4088), the register path's type, without two 65536-bit images and the per-word
-      //      emission loops.  In this kernel, not the copy + filter one (there it made the L2-bound light
-      //      kernel the long pole: profiles/r05/merge).
-      merge_stage(pq, tc.cp, qq, tc.cq, s, lane);
-      __builtin_amdgcn_sched_barrier(0);
-      { // the staged payloads' registers are free: the next task's loads go out now
-        const bool real = has_next && !tn.bigq;
-        load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, lane);
-      }
-      load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, lane);
-      c = (int)merge_run<OP, !CARD_ONLY>(s, tc.cp, tc.cq, reinterpret_cast<uint16_t *>(dst), lane);
-      ty = CARD_ONLY ? (c ? kArray : kEmpty) : (c || (OP == RB_XOR && tm.keep_empty)) ? kArray : kEmpty;
-      nr = 0;
-      done = true;
-    }
     if (ROLE == kRoleHeavy && !done) {
       // ---- the result as a register bitmap: P = A, Q = B (never swapped: ANDNOT and the type
       //      rules are ordered)
-#if RBG_STUDY
-      {
-        const uint64_t tw0 = __builtin_amdgcn_s_memtime();
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
-        lt_wait += __builtin_amdgcn_s_memtime() - tw0;
-      }
-#endif
       uint64_t w[kW];
       if (bitmap_payload(tc.tp, tc.cp)) {
 #pragma unroll
@@ -1191,7 +1092,6 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       }
       // ---- both next payloads in flight during classification and emission (the fence keeps the
       //      scheduler from hoisting these loads above the consumption of the current ones)
-      RBG_HT(lt2 = __builtin_amdgcn_s_memtime(); lt_acc[1] += lt2 - lt1);
       __builtin_amdgcn_sched_barrier(0);
       {
         const bool real = has_next && !tn.bigq;
@@ -1203,7 +1103,6 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       const bool eff = eff_rule<OP>(ta, tb, tc.cp, tc.cq);
       int r;
       metrics(w, lane, (eff || (lazy && (ta == kRun || tb == kRun))) && !CARD_ONLY, c, r);
-      RBG_HT(const uint64_t lt3 = __builtin_amdgcn_s_memtime(); lt_acc[2] += lt3 - lt2; lt2 = lt3);
       bool bits = false;
       if (lazy) {
         ty = lazy_or_type(tm.lazy, ta, tb, tc.cp, tc.cq, c, r, cw, bits);
@@ -1218,18 +1117,16 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       } else ty = type_ab(c);
       if (CARD_ONLY) ty = c ? kArray : kEmpty;
       else if (ty != kEmpty) {
-        if (RBG_BAL_EMIT) emit_container_bal(bits ? (int)kBitmap : ty, w, c, r, dst, s, estage[wv], lane);
-        else emit_container(bits ? (int)kBitmap : ty, w, c, r, dst, s, lane);
+        emit_container(bits ? (int)kBitmap : ty, w, c, r, dst, s, lane);
       }
       nr = ty == kRun ? (uint32_t)r : 0u;
-      RBG_HT(lt_acc[3 + (ty == kBitmap ? 0 : ty == kArray ? 1 : 2)] += __builtin_amdgcn_s_memtime() - lt2);
     } else if (ROLE != kRoleHeavy) {
-      // ---- phase 1: stage X (filter; kBits: the other operand) or store the clone (copy)
-      if (tc.kind == kFilter || tc.kind == kBits) {
+      // ---- phase 1: stage X (filter) or store the clone (copy)
+      if (tc.kind == kFilter) {
         if (tc.bigq) stage_big_runs(tc.pq, tc.rq, s, fresh(lane)); // only a Run payload exceeds 8 KiB
-        // a filter probes a Run X by parity on the carry-folded toggle image; kBits ORs membership words (and
-        // stage_big_runs always leaves those: the filter below picks its probe by the same condition)
-        else stage_from_chunks(tc.tq, qq, tc.cq, tc.rq, s, fresh(lane), tc.kind == kFilter);
+        // a filter probes a Run X by parity on the carry-folded toggle image (stage_big_runs always leaves
+        // membership words: the filter below picks its probe by the same condition)
+        else stage_from_chunks(tc.tq, qq, tc.cq, tc.rq, s, fresh(lane), true);
       } else if (!CARD_ONLY) {
         if (tc.bigp) {
           copy_payload(tc.pp, dst, tc.pbytes, fresh(lane), qq); // Q's registers: a copy has no Q
@@ -1244,7 +1141,6 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
         const bool real = has_next && tn.kind != kCopy && !tn.bigq;
         load_chunks(qq, real ? tn.pq : tn.pp, real ? tn.qbytes : 16u, fresh(lane));
       }
-      RBG_LT(lt2 = __builtin_amdgcn_s_memtime(); lt_acc[tc.kind == kFilter ? 1 + (tc.tq == kBitmap ? 0 : tc.tq == kArray ? 1 : 2) : 4] += lt2 - lt1);
       // ---- phase 2: filter F against the staged X, in value order (adjacent lanes, adjacent values)
       //      through a linear per-wave stage.  (Streaming the next F into pq row by row as the filter
       //      frees it measured 7% slower: loads and the staged stores share vmcnt, so the loads issued
@@ -1257,40 +1153,11 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
           c = filter_rows_linear<kNeg, !CARD_ONLY, true>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane));
         else c = filter_rows_linear<kNeg, !CARD_ONLY, false>(pq, (int)tc.cp, s, ob, tb, o, fresh(lane));
         ty = c ? kArray : kEmpty;
-      } else if (tc.kind == kBits) {
-        // ---- OR into the large Bitmap P (bits_task): the rows ORed and counted first, then stored — as the
-        //      Bitmap, or as the full Run (one run [0, 65535], 16-B padded) unless Bitmap.ior(Array) keeps it
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(s);
-        uint32_t cl = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const uint4 x = s4[k * 64 + lane];
-          pq[k] = make_uint4(pq[k].x | x.x, pq[k].y | x.y, pq[k].z | x.z, pq[k].w | x.w);
-          cl += __popc(pq[k].x) + __popc(pq[k].y) + __popc(pq[k].z) + __popc(pq[k].w);
-        }
-        c = (int)wave_sum_u32(cl);
-        const bool keep_bitmap = tm.inplace && tc.p_is_a && tc.tq == kArray;
-        ty = c == kSpan && !keep_bitmap ? kRun : kBitmap;
-        nr = ty == kRun ? 1u : 0u;
-        if (!CARD_ONLY) {
-          uint4 *o4 = reinterpret_cast<uint4 *>(dst);
-          if (ty == kRun) {
-            if (lane == 0) o4[0] = make_uint4(0xFFFF0000u, 0u, 0u, 0u);
-          } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) o4[k * 64 + lane] = pq[k];
-          }
-        }
-        if (CARD_ONLY) { // the card-only kernels mark a non-empty result as an Array (as the register path)
-          ty = kArray;
-          nr = 0;
-        }
       } else {
         ty = tc.tp;
         c = (int)tc.cp;
         nr = tc.rp;
       }
-      RBG_LT(lt_acc[5] += __builtin_amdgcn_s_memtime() - lt2);
       load_chunks(pq, tn.pp, tn.bigp ? 16u : tn.pbytes, fresh(lane));
     }
     wave_lds_sync(); // the next task restages the same LDS image
@@ -1298,21 +1165,11 @@ __global__ __launch_bounds__(256, ROLE == kRoleHeavy ? kHeavyWaves : kLightWaves
       tm.type[cur.t] = (uint8_t)ty;
       tm.res[cur.t] = task_res((uint32_t)ty, nr, cw != 0xFFFFFFFFu ? cw : (uint32_t)c);
     }
-    RBG_LT(lt_acc[6] += __builtin_amdgcn_s_memtime() - lt0; ++lt_acc[7]);
-    RBG_HT(lt_acc[6] += __builtin_amdgcn_s_memtime() - lt0; ++lt_acc[7]);
     if (!has_next) break;
     g = gn;
     cur = nx;
     tc = tn;
   }
-#if RBG_STUDY
-  if (ROLE == kRoleLight && lane == 0 && wv == 0 && blockIdx.x % 97 == 0)
-    printf("light timing blk %u: decode %lu stageB %lu stageA %lu stageR %lu copy %lu filter %lu iter %lu tasks %lu\n",
-           blockIdx.x, lt_acc[0], lt_acc[1], lt_acc[2], lt_acc[3], lt_acc[4], lt_acc[5], lt_acc[6], lt_acc[7]);
-  if (ROLE == kRoleHeavy && lane == 0 && wv == 0 && blockIdx.x % 61 == 0)
-    printf("heavy timing op %d blk %u: decode %lu build %lu (payload wait %lu) metrics %lu emitB %lu emitA %lu emitR %lu iter %lu tasks %lu\n",
-           OP, blockIdx.x, lt_acc[0], lt_acc[1], lt_wait, lt_acc[2], lt_acc[3], lt_acc[4], lt_acc[5], lt_acc[6], lt_acc[7]);
-#endif
 }
 
 // ---------------------------------------------------------------- measurement probes
@@ -1336,7 +1193,7 @@ __global__ __launch_bounds__(256, 4) void k_probe_tasks(const uint8_t *__restric
   uint64_t g = (uint64_t)blockIdx.x * 4 + wv;
   if (g >= n) return;
   RecU cur = load_rec(recs + g);
-  Task tc = decode_task<OP, false>(cur, pay_a, pay_b);
+  Task tc = decode_task<OP>(cur, pay_a, pay_b);
   uint4 pq[8], qq[8];
   load_chunks(pq, tc.pp, tc.bigp ? 16u : tc.pbytes, lane);
   if (tc.kind == kCopy || tc.bigq) load_chunks(qq, tc.pp, 16, lane);
@@ -1346,7 +1203,7 @@ __global__ __launch_bounds__(256, 4) void k_probe_tasks(const uint8_t *__restric
     const uint64_t gn = g + stride;
     const bool has_next = gn < n;
     const RecU nx = load_rec(recs + (has_next ? gn : g));
-    const Task tn = decode_task<OP, false>(nx, pay_a, pay_b);
+    const Task tn = decode_task<OP>(nx, pay_a, pay_b);
     acc ^= fold_chunks(qq);
     {
       const bool real = has_next && tn.kind != kCopy && !tn.bigq;
@@ -1585,16 +1442,12 @@ static void launch_tasks(const uint8_t *pa, const uint8_t *pb, const TaskRec *re
                          const TaskMeta &tm, hipStream_t st, unsigned per_cu = 0,
                          unsigned long long *queue = nullptr) {
   if (!n) return;
-#ifndef RBG_LDS_PAD
-#define RBG_LDS_PAD 0 // study: dynamic LDS a light block reserves without using it (occupancy sensitivity)
-#endif
-  const size_t dyn = ROLE == kRoleLight ? RBG_LDS_PAD : 0;
   static unsigned occ_cap = 0; // occupancy-derived grid cap, per template instance
   if (!occ_cap) occ_cap = persistent_blocks(k_pair_tasks<OP, CARD_ONLY, ROLE>, ~0ull >> 8);
   const unsigned cap = per_cu ? std::min(occ_cap, per_cu * cu_count()) : occ_cap;
   const uint64_t want = (n + 3) / 4;
   const unsigned blocks = (unsigned)(want < cap ? want : cap);
-  k_pair_tasks<OP, CARD_ONLY, ROLE><<<blocks, 256, dyn, st>>>(pa, pb, recs, n, out, tm, queue);
+  k_pair_tasks<OP, CARD_ONLY, ROLE><<<blocks, 256, 0, st>>>(pa, pb, recs, n, out, tm, queue);
 }
 template <int OP>
 static void launch_op(bool card_only, const uint8_t *pa, const uint8_t *pb, const TaskRec *light, uint64_t nl,
@@ -1706,11 +1559,6 @@ __device__ __forceinline__ uint32_t meta_cw(uint64_t m) {
 // The compaction, run by the last block of k_pair_small: drop the empty slots, write the result SoA and
 // CSR (slot t's payload stays at t * 8 KiB), add up the blocks' counters and write the call's result words
 // to host-visible memory.  xl: the block's LDS scratch (the slot -> result position map when E fits it).
-#if RBG_SMALL_STUDY
-#define RBG_SS(i) if (threadIdx.x == 0) g_small_study[8191 * kStudyWords + (i)] = __builtin_amdgcn_s_memrealtime()
-#else
-#define RBG_SS(i)
-#endif
 constexpr uint32_t kSmallXposLds = 8192;
 constexpr uint32_t kXposEmpty = 1u << 31; // xpos flag: the slot holds no result (positions stay < 2^31)
 template <class Tab>
@@ -1718,7 +1566,6 @@ __device__ void small_compact(const SmallPairArgs &a, const Tab &tab, uint32_t *
   const uint32_t nt = blockDim.x, E = a.E;
   uint32_t *xpos = E <= kSmallXposLds ? xl : a.xpos;
   const OutView &out = a.out;
-  RBG_SS(0);
   // the result CSR's first slot table entry and the first tile of slot words: independent loads first
   const uint32_t slot_own = a.rbegin && threadIdx.x <= a.np ? tab.slot_at(threadIdx.x) : 0u;
   // the call's counters, summed from the slot words: input bytes (with the key arrays), key-array bytes, output
@@ -1803,13 +1650,11 @@ __device__ void small_compact(const SmallPairArgs &a, const Tab &tab, uint32_t *
     base = rb;
     __syncthreads(); // the row totals are read; the next tile rewrites them
   }
-  RBG_SS(1);
   if (a.rbegin)
     for (uint32_t p = threadIdx.x; p <= a.np; p += nt) {
       const uint32_t t = p == threadIdx.x ? slot_own : tab.slot_at(p);
       a.rbegin[p] = t < E ? xpos[t] & ~kXposEmpty : base;
     }
-  RBG_SS(2);
   if (a.pcard) // per-pair result cardinality (RoaringBitmap.andCardinality etc.)
     for (uint32_t p = threadIdx.x; p < a.np; p += nt) {
       uint64_t c = 0;
@@ -1823,7 +1668,6 @@ __device__ void small_compact(const SmallPairArgs &a, const Tab &tab, uint32_t *
   // release: the host may return as soon as it reads that number (pairwise_small), before the kernel's
   // end is signalled
   uint64_t *vs = reinterpret_cast<uint64_t *>(wtot);
-  RBG_SS(3);
   __syncthreads(); // wtot's last readers (the scans) are done
   {
     const uint64_t s0 = wave_sum_u64(pin + pkey), s1 = wave_sum_u64(pkey), s2 = wave_sum_u64(pout), s3 = wave_sum_u64(pcs);
@@ -1836,7 +1680,7 @@ __device__ void small_compact(const SmallPairArgs &a, const Tab &tab, uint32_t *
   }
   const bool fail = __syncthreads_or(bad);
   if (threadIdx.x == 0) {
-    __hip_atomic_store(a.ctr, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // ready for the next call
+    __hip_atomic_store(a.ctr, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // zero between calls
     if (!fail) {
       for (int k = 0; k < 4; ++k) {
         uint64_t t = 0;
@@ -1851,7 +1695,6 @@ __device__ void small_compact(const SmallPairArgs &a, const Tab &tab, uint32_t *
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __hip_atomic_store(a.hout + 5, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    RBG_SS(4);
   }
   // the slot words back to kSlotUnset for the next call, after the hand-off (the next kernel on the stream starts
   // after this one ends; after a failed call the host resets them, seq_end)
@@ -1870,20 +1713,11 @@ constexpr int kSmallLdsMax = 96 * 1024; // >= small_lds_bytes(4, kSmallPairKeys)
 __host__ __device__ constexpr uint32_t small_lds_bytes(uint32_t waves, uint32_t kmax) {
   return waves * 8192u + 256u + 4u * kmax + 2u * kmax + 2u * (kmax + 1) + 2u * kmax + 16u;
 }
-#ifndef RBG_SMALL_ONE_STAGE
-#define RBG_SMALL_ONE_STAGE 1 // study builds: 0 inlines the staging code once per operand
-#endif
 constexpr int kSmallWaves = 2; // waves per SIMD of the small-batch kernel (the register path takes ~235 VGPRs; 3 and 4 spill)
 template <int OP, bool CARD_ONLY, class Tab>
 __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a, uint32_t kmax, Tab tab) {
   extern __shared__ __attribute__((aligned(16))) uint8_t dyn_lds[];
   __shared__ uint32_t s_last;
-#if RBG_SMALL_STUDY
-  __shared__ uint64_t s_t[8];
-  __shared__ uint32_t s_keys[4];
-  __shared__ uint64_t s_slow[4][3];
-  if (threadIdx.x == 0) s_t[0] = __builtin_amdgcn_s_memrealtime();
-#endif
   const uint32_t nw = blockDim.x >> 6;
   uint32_t *wtot = reinterpret_cast<uint32_t *>(dyn_lds + nw * 8192u); // [64] block-scan wave totals / row totals
   uint32_t *ent = wtot + 64; // merged key: A index | B index << 16
@@ -1915,21 +1749,9 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
   const bool ident = tab.same(p); // x1.op(x1) in place
   const uint64_t i0 = tab.a0(p), j0 = tab.b0(p);
   const uint32_t na = tab.counts(p) & 0xFFFFu, nb = tab.counts(p) >> 16;
-#ifndef RBG_SMALL_TICKET
-#define RBG_SMALL_TICKET 0 // study builds: 1 elects the compaction block by a start ticket instead of the last block id
-#endif
-#if RBG_SMALL_TICKET
-  // the block's start ticket (the compaction's election, below), its round trip beside the key loads'
-  uint64_t tk = 0;
-  if (threadIdx.x == 0) tk = __hip_atomic_fetch_add(a.ctr, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
   for (uint32_t t = threadIdx.x; t < na; t += nt) K[t] = a.A.key[i0 + t];
   for (uint32_t t = threadIdx.x; t < nb; t += nt) K[na + t] = a.B.key[j0 + t];
-#if RBG_SMALL_TICKET
-  if (threadIdx.x == 0) s_last = tk == a.nblocks - 1ull;
-#else
   if (threadIdx.x == 0) s_last = blockIdx.x == gridDim.x - 1;
-#endif
   __syncthreads();
   const uint16_t *KA = K, *KB = K + na;
   // ---- merged key order (RoaringBitmap.and/or/xor/andNot key loops, RoaringBitmap.java:377-473,
@@ -1974,11 +1796,6 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
     __syncthreads();
   }
   // ---- one wave per merged key
-#if RBG_SMALL_STUDY
-  if (threadIdx.x == 0) s_t[1] = __builtin_amdgcn_s_memrealtime();
-  uint32_t st_keys = 0;
-  uint64_t sl_dur = 0, sl_d1 = 0, sl_d2 = 0;
-#endif
   uint32_t *s = reinterpret_cast<uint32_t *>(dyn_lds) + wv * 2048;
   const uint32_t slot0 = tab.slot_at(p), slot1 = tab.slot_at(p + 1);
   // slots past the merged keys hold nothing
@@ -1992,10 +1809,6 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
     const uint32_t pos = (k & 1) ? (k + 1) * W - 1 - gw : k * W + gw;
     if (pos >= nu) continue;
     const uint32_t e = ord[pos];
-#if RBG_SMALL_STUDY
-    ++st_keys;
-    const uint64_t st_k0 = __builtin_amdgcn_s_memrealtime();
-#endif
     const uint32_t en = ent[e], ia = en & 0xFFFF, ib = en >> 16;
     const bool has_a = ia != 0xFFFFu, has_b = ib != 0xFFFFu;
     const uint32_t kkey = has_a ? KA[ia] : KB[ib];
@@ -2011,13 +1824,12 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
         st_sc1(a.smeta + kSmallSlots + slot, (uint64_t)inb_ | ((uint64_t)c_ << 32));
       }
     };
-    if (RBG_SMALL_MERGE && has_a && has_b && !ident && a.A.type[i0 + ia] == kArray &&
+    if (has_a && has_b && !ident && a.A.type[i0 + ia] == kArray &&
         a.B.type[j0 + ib] == kArray && !(OP == RB_OR && a.lazy) && a.A.card[i0 + ia] + a.B.card[j0 + ib] <= kMergeMax) {
       // two Arrays: the merge (merge_run), an Array result
       const uint64_t xa = i0 + ia, xb = j0 + ib;
       const uint32_t ca = a.A.card[xa], cb = a.B.card[xb];
       const uint32_t kin = (uint32_t)(alg_bytes(kArray, ca, 0) + alg_bytes(kArray, cb, 0) + 32);
-      RBG_MT(5);
       {
         uint4 q[8], r[8];
         load_chunks(q, a.A.payload + a.A.off[xa], 2u * ca, lane);
@@ -2027,7 +1839,6 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
       auto mty = [&](uint32_t n) { return n || (OP == RB_XOR && a.keep_empty && !CARD_ONLY) ? (int)kArray : (int)kEmpty; };
       c = (int)merge_run<OP, !CARD_ONLY>(s, ca, cb, reinterpret_cast<uint16_t *>(dst), lane,
                                          [&](uint32_t n) { publish(mty(n), n, 0u, 0xFFFFFFFFu, kin); });
-      RBG_MT(6);
       ty = mty((uint32_t)c);
     } else if (has_a && has_b && !ident) {
       const uint64_t xa = i0 + ia, xb = j0 + ib;
@@ -2037,7 +1848,6 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
       const uint32_t ba = (uint32_t)payload_bytes(ta, ca, ra), bb = (uint32_t)payload_bytes(tb, cb, rb);
       const uint32_t kin = (uint32_t)(alg_bytes(ta, ca, ra) + alg_bytes(tb, cb, rb) + 32);
       uint64_t w[kW];
-#if RBG_SMALL_ONE_STAGE
       // both operands through ONE copy of the staging code (a loop of two): this kernel's code (82 KB, of which
       // each staging copy ~17 KB) outgrew the instruction cache, and its misses sat on the slowest keys' path
       // (SQC_ICACHE_MISSES, profiles/r06/small)
@@ -2074,38 +1884,6 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
           }
         }
       }
-#else
-      uint4 q[8];
-      if (bitmap_payload(ta, ca)) {
-        load_bitmap(pa, w, lane);
-      } else {
-        if (ba > (uint32_t)kBitmapBytes) stage_big_runs(pa, ra, s, lane);
-        else {
-          load_chunks(q, pa, ba, lane);
-          stage_from_chunks(ta, q, ca, ra, s, lane);
-        }
-        lds_read_words(s, w, lane);
-        wave_lds_sync();
-      }
-      if (bitmap_payload(tb, cb)) {
-        load_chunks(q, pb, kBitmapBytes, lane);
-      } else {
-        if (bb > (uint32_t)kBitmapBytes) stage_big_runs(pb, rb, s, lane);
-        else {
-          load_chunks(q, pb, bb, lane);
-          stage_from_chunks(tb, q, cb, rb, s, lane);
-        }
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(s);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) q[k] = s4[k * 64 + lane];
-        wave_lds_sync();
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        word_op<OP>(w[2 * k], pack2(q[k].x, q[k].y));
-        word_op<OP>(w[2 * k + 1], pack2(q[k].z, q[k].w));
-      }
-#endif
       const bool lazy = OP == RB_OR && a.lazy;
       const bool eff = eff_rule<OP>(ta, tb, ca, cb);
       int r;
@@ -2140,80 +1918,16 @@ __global__ __launch_bounds__(256, kSmallWaves) void k_pair_small(SmallPairArgs a
     } else {
       publish(kEmpty, 0u, 0u, 0xFFFFFFFFu, 0u); // a key the op drops
     }
-#if RBG_SMALL_STUDY
-    {
-      const uint64_t d = __builtin_amdgcn_s_memrealtime() - st_k0;
-      if (d > sl_dur) {
-        const uint32_t ta = has_a ? a.A.type[i0 + ia] : 3u, tb = has_b ? a.B.type[j0 + ib] : 3u;
-        const uint32_t ca = has_a ? a.A.card[i0 + ia] : 0u, cb = has_b ? a.B.card[j0 + ib] : 0u;
-        const uint32_t ra = has_a ? a.A.nruns[i0 + ia] : 0u, rb = has_b ? a.B.nruns[j0 + ib] : 0u;
-        sl_dur = d;
-        if (lane == 0) { // merge phases relative to the key's start (0 when the key took no merge)
-          const uint64_t *mt = g_merge_ts[min(blockIdx.x, 8191u) * 4 + wv];
-          const uint64_t tend = __builtin_amdgcn_s_memrealtime();
-          g_small_study[min(blockIdx.x, 8191u) * kStudyWords + 19 + 4 * wv] =
-              mt[5] >= st_k0 ? ((mt[5] - st_k0) | (mt[1] - mt[5]) << 10 | (mt[2] - mt[1]) << 20 | (mt[3] - mt[2]) << 30 |
-                                (mt[4] - mt[3]) << 40 | (mt[6] - mt[4]) << 50)
-                             : 0ull;
-          g_small_study[min(blockIdx.x, 8191u) * kStudyWords + 31 - wv] = mt[6] >= st_k0 ? tend - mt[6] : 0ull;
-        }
-        sl_d1 = ta | (tb << 2) | ((uint64_t)(ty & 0xFF) << 8) | ((uint64_t)(nr & 0xFFFF) << 16) | ((uint64_t)(uint32_t)c << 32);
-        sl_d2 = (uint64_t)ca | ((uint64_t)cb << 20) | ((uint64_t)(ra & 0xFFF) << 40) | ((uint64_t)(rb & 0xFFF) << 52);
-      }
-    }
-#endif
   }
-#if RBG_SMALL_STUDY
-  if (lane == 0) {
-    s_keys[wv] = st_keys;
-    s_t[2 + wv] = __builtin_amdgcn_s_memrealtime();
-    s_slow[wv][0] = sl_dur;
-    s_slow[wv][1] = sl_d1;
-    s_slow[wv][2] = sl_d2;
-  }
-#endif
-  // ---- the last block compacts (s_last; RBG_SMALL_TICKET: the last to start): it is the only block that waits,
+  // ---- the block with the last id compacts (s_last): it is the only block that waits,
   //      and the blocks it waits for wait on nothing, so they finish whatever the dispatch order (its polls are
   //      bounded besides); the others just end, their payload stores in flight (nothing in the launch reads a
   //      payload; the stream contract covers the rest, wait_call_seq)
-#if RBG_SMALL_STUDY
-  __syncthreads();
-  uint64_t *gs = g_small_study + (uint64_t)min(blockIdx.x, 8191u) * kStudyWords;
-  if (threadIdx.x == 0) {
-    gs[0] = s_t[0];
-    gs[1] = s_t[1];
-    for (int w = 0; w < 4; ++w) gs[2 + w] = s_t[2 + w];
-    for (int w = 0; w < 4; ++w) gs[6 + w] = s_keys[w];
-    gs[10] = __builtin_amdgcn_s_memrealtime();
-    gs[11] = 0;
-    gs[12] = p;
-    gs[13] = sub | ((uint64_t)nsub << 32);
-    gs[14] = nu;
-    gs[15] = s_last;
-    for (int w = 0; w < 4; ++w) {
-      gs[16 + 4 * w] = s_slow[w][0];
-      gs[17 + 4 * w] = s_slow[w][1];
-      gs[18 + 4 * w] = s_slow[w][2];
-    }
-  }
-#else
   if (!s_last) return;
   __syncthreads(); // the block's waves are past their scratch use
-#endif
-  if (!s_last) return;
+  if (!s_last) return; // (read again past the barrier, as the product always compiled it)
   small_compact(a, tab, reinterpret_cast<uint32_t *>(dyn_lds), wtot);
-#if RBG_SMALL_STUDY
-  __syncthreads();
-  if (threadIdx.x == 0) gs[11] = __builtin_amdgcn_s_memrealtime();
-#endif
 }
-#if RBG_SMALL_STUDY
-} // namespace rbg
-extern "C" int rbgpu_internal_small_study(uint64_t *host, uint64_t words) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(rbg::g_small_study), words * 8) == hipSuccess ? 0 : -1;
-}
-namespace rbg {
-#endif
 
 template <int OP, bool CARD_ONLY, class Tab>
 static void launch_small_tab(const SmallPairArgs &a, const Tab &tab, unsigned waves, unsigned nblocks, uint32_t kmax,

@@ -33,9 +33,6 @@ static uint32_t pairwise_seg_keys(const rbgpu_set *a, const rbgpu_set *b, uint64
 static inline uint64_t bm_conts(const rbgpu_set *s, uint32_t i) {
   return i == kEmptyBitmap ? 0 : s->h_begin[i + 1] - s->h_begin[i];
 }
-#ifndef RBG_SMALL_POLL
-#define RBG_SMALL_POLL 1 // study builds: 0 waits for the stream
-#endif
 static int pairwise_small(rbgpu_ctx *ctx, int op, const rbgpu_set *a, const rbgpu_set *b, const uint32_t *a_idx,
                           const uint32_t *b_idx, uint32_t np, rbgpu_set **out, uint64_t *card_out, bool inplace,
                           bool keep_empty) {
@@ -142,7 +139,6 @@ static int pairwise_small(rbgpu_ctx *ctx, int op, const rbgpu_set *a, const rbgp
   stats_begin(ctx, false);
   if (ktimes) HIPCHK(hipEventRecord(ctx->ev[1], st));
   sa.E = (uint32_t)E;
-  sa.nblocks = nblocks;
   sa.xpos = xpos;
   sa.rbegin = res ? res->begin : nullptr;
   if (res) sa.out = OutView{res->key, res->type, res->card, res->nruns, res->off};
@@ -158,7 +154,7 @@ static int pairwise_small(rbgpu_ctx *ctx, int op, const rbgpu_set *a, const rbgp
   // The last block writes the result words to host memory and then the call's sequence number
   // (wait_call_seq); per-pair cardinalities come back by a copy, so those calls wait for the stream.
   bool seen = false;
-  if ((rc = seq_end(ctx, sa.seq, RBG_SMALL_POLL && !card_out, "small-batch pairwise", &seen))) return rc;
+  if ((rc = seq_end(ctx, sa.seq, !card_out, "small-batch pairwise", &seen))) return rc;
   // the result words, written by the last block straight into host memory
   uint64_t *w = ctx->words;
   for (int i = 0; i < kStatWords; ++i) w[i] = 0;
@@ -185,10 +181,6 @@ static int pairwise_small(rbgpu_ctx *ctx, int op, const rbgpu_set *a, const rbgp
 // (58 B per task: 464 MiB at the cap; the bound a.nc + b.nc can far exceed the real count — an AND of
 // mostly disjoint keys — and the workspace stays grown, so the cap is set just above config 2's 6.1M)
 constexpr uint64_t kEarlyEmitTasks = 1ull << 23;
-
-#ifndef RBG_FORCE_SERIAL
-#define RBG_FORCE_SERIAL 0 // study: light then heavy on one stream (each kernel's standalone time)
-#endif
 
 // One general-pipeline call: its arguments and what each phase leaves for the next.
 struct PairCall {
@@ -432,7 +424,7 @@ int emit_tasks(PairCall &c) {
   }
   // the light and heavy task kernels run concurrently (heavy on the side stream, 1 block per CU;
   // light 2 blocks per CU: 2 x 128 + 256 VGPRs per SIMD)
-  c.conc = !RBG_FORCE_SERIAL && !c.o.probe && c.nlight && c.nheavy &&
+  c.conc = !c.o.probe && c.nlight && c.nheavy &&
            c.nlight + c.nheavy >= 65536; // small batches: the cross-stream waits cost more than the overlap
   // the emit zeroes the queue counters before ev[1]: the side stream waits on ev[1] before its light launch
   if (!c.early)

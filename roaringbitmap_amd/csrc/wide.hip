@@ -660,12 +660,13 @@ int wide_run(rbgpu_ctx *ctx, int sem, const rbgpu_set *in, const std::vector<uin
   const bool fast_sem = sem == RB_FAST_OR || sem == RB_WORKSHY_AND || sem == RB_FAST_XOR;
   bool fast_ok = fast_sem && !getenv("RBGPU_NO_RUN_FASTPATH"); // parity tests run both paths
   if (fast_ok && (sem == RB_WORKSHY_AND || sem == RB_FAST_XOR)) {
-    // workShyAnd / naive_xor fast paths read packed records; naive_xor's key-major ones for a dense set
-    // in set order are the set's cached krec
+    // naive_xor's fast path reads packed records; its key-major ones for a dense set in set order are the
+    // set's cached krec
     // (a dense set's krec is built from its SoA when it has no mrec: naive_xor then never needs mrec)
+    // workShyAnd builds none: it reads the set's SoA unless the set already has an mrec
     if (in->payload_bytes >= kRecMaxPayload) fast_ok = false;
     else if (sem == RB_FAST_XOR && dense && identity) fast_ok = !ensure_krec(in);
-    else if (!(RBG_AND_SOA && sem == RB_WORKSHY_AND) && ensure_mrec(in)) fast_ok = false;
+    else if (sem == RB_FAST_XOR && ensure_mrec(in)) fast_ok = false;
   }
   (void)hipGetLastError();
 

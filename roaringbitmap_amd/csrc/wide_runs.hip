@@ -242,13 +242,11 @@ __global__ __launch_bounds__(256) void k_wide_runs(SetView s, CidMap cm,
 // latency per step).  A key with another container type, > 8 runs or a list overflow is routed to the
 // generic kernel (route[q] = 1): results are identical.
 constexpr int kAndCap = 16;
-#ifndef RBG_AND_RING
-#define RBG_AND_RING 2 // steps every link of the load chain spans (at 32 keys: 2 1.55, 3 1.64, 4 1.67 ms)
-#endif
-constexpr int kAndDc = RBG_AND_RING; // steps between a container id's load and its record's load
-constexpr int kAndDr = RBG_AND_RING; // steps between a record's load and its runs' load
-constexpr int kAndDp = RBG_AND_RING; // steps between the runs' load and their use
-constexpr int kAndU = 2 * RBG_AND_RING; // steps per unrolled loop trip: a multiple of Dp, Dp + Dr and Dc
+constexpr int kAndRing = 2; // steps every link of the load chain spans (at 32 keys: 2 1.55, 3 1.64, 4 1.67 ms)
+constexpr int kAndDc = kAndRing; // steps between a container id's load and its record's load
+constexpr int kAndDr = kAndRing; // steps between a record's load and its runs' load
+constexpr int kAndDp = kAndRing; // steps between the runs' load and their use
+constexpr int kAndU = 2 * kAndRing; // steps per unrolled loop trip: a multiple of Dp, Dp + Dr and Dc
 static_assert(kAndU % kAndDp == 0 && kAndU % (kAndDp + kAndDr) == 0 && kAndU % kAndDc == 0, "ring periods");
 struct AndMeta {
   uint32_t typ, nr;
@@ -550,10 +548,8 @@ __global__ __launch_bounds__(256) void k_wide_runs_and(SetView s, const uint64_t
   }
 }
 
-#ifndef RBG_AND_KEYS
-#define RBG_AND_KEYS 32 // keys per wave (round 6 A/B, profiles/r06/and: 8 2.14, 16 1.80, 32 1.64, 64 1.94 ms)
-#endif
-constexpr int kAndKeys = RBG_AND_KEYS; // keys per wave of the lane-parallel workShyAnd
+// keys per wave of the lane-parallel workShyAnd (round 6 A/B, profiles/r06/and: 8 2.14, 16 1.80, 32 1.64, 64 1.94 ms)
+constexpr int kAndKeys = 32;
 
 bool launch_wide_runs(int sem, const SetView &s, const uint64_t *mrec, const CidMap &cm, const uint64_t *seg,
                       const uint32_t *klist, uint32_t nk, uint8_t *out, const WideOut &wo, uint8_t *route,
@@ -562,8 +558,7 @@ bool launch_wide_runs(int sem, const SetView &s, const uint64_t *mrec, const Cid
   switch (sem) {
   case RB_FAST_OR: k_wide_runs<RB_FAST_OR><<<g, 256, 0, st>>>(s, cm, seg, klist, nk, out, wo, route, stats); return true;
   case RB_WORKSHY_AND: {
-    // no mrec: the SoA-reading kernel (RBG_AND_SOA builds, wide.hip then builds no records)
-    if (!mrec && !RBG_AND_SOA) return false;
+    // no mrec: the SoA-reading kernel (wide.hip builds no records for workShyAnd)
     const unsigned waves = (nk + kAndKeys - 1) / kAndKeys, gb = (waves + 3) / 4;
     if (cm.cid) {
       if (mrec) k_wide_runs_and<kAndKeys, false, false><<<gb, 256, 0, st>>>(s, mrec, cm, seg, klist, nk, out, wo, route, stats);

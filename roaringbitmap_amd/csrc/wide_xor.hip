@@ -249,54 +249,10 @@ __global__ __launch_bounds__(256) void k_records_direct2(SetView s, const uint64
       *reinterpret_cast<uint2 *>(rec + (uint64_t)(kw - key_lo) * M + i) = make_uint2(tile[2 * lx][r], tile[2 * lx + 1][r]);
   }
 }
-// The same with 256-key x 32-member tiles, four containers per lane (8-B run-count quads, two 16-B offset pairs):
-// a member's load row is 2 KiB of offsets (a whole HBM page) and 512 B of run counts, and a key's store row one
-// 128-B line.  Needs container indices and the key count in fours (quads, build_krec_range).
-#ifndef RBG_REC_QUAD
-#define RBG_REC_QUAD 0 // study builds: 1 builds dense records by the 256 x 32 tiles
-#endif
-__global__ __launch_bounds__(256) void k_records_direct4(SetView s, const uint64_t *__restrict__ mbase, uint64_t bias,
-                                                         uint32_t M, uint32_t key_lo, uint32_t key_hi,
-                                                         uint32_t *__restrict__ rec) {
-  __shared__ uint32_t tile[32][257]; // [member][key]
-  const uint32_t k0 = key_lo + blockIdx.x * 256, m0 = blockIdx.y * 32;
-  const uint32_t t = threadIdx.x, kx = t & 63, ry = t >> 6;
-  uint64_t rb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) rb[j] = mbase[min(m0 + ry + 4 * j, M - 1)] - bias;
-  const uint32_t k = min(k0 + 4 * kx, key_hi - 4);
-  uint2 nr[8];
-  uint4 o0[8], o1[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { // all 24 loads in flight at once
-    const uint64_t i = rb[j] + k;
-    nr[j] = *reinterpret_cast<const uint2 *>(s.nruns + i);
-    o0[j] = *reinterpret_cast<const uint4 *>(s.off + i);
-    o1[j] = *reinterpret_cast<const uint4 *>(s.off + i + 2);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const uint32_t n[4] = {nr[j].x & 0xFFFFu, nr[j].x >> 16, nr[j].y & 0xFFFFu, nr[j].y >> 16};
-    const uint64_t o[4] = {o0[j].x | ((uint64_t)o0[j].y << 32), o0[j].z | ((uint64_t)o0[j].w << 32),
-                           o1[j].x | ((uint64_t)o1[j].y << 32), o1[j].z | ((uint64_t)o1[j].w << 32)};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) tile[ry + 4 * j][4 * kx + u] = pack_xrec(n[u] != 0, n[u], o[u]);
-  }
-  __syncthreads();
-  const uint32_t lx = t & 31, rr = t >> 5; // a key row is 32 members x 4 B: 8 rows per pass
-  const uint32_t i = m0 + lx;
-  for (uint32_t r = rr; r < 256; r += 8) {
-    const uint32_t kw = k0 + r;
-    if (i < M && kw < key_hi) rec[(uint64_t)(kw - key_lo) * M + i] = tile[lx][r];
-  }
-}
 void launch_records_direct(const SetView &s, const uint64_t *mbase, uint64_t bias, uint32_t M, uint32_t key_lo,
-                           uint32_t key_hi, uint32_t *rec, hipStream_t st, bool pairs, bool quads) {
+                           uint32_t key_hi, uint32_t *rec, hipStream_t st, bool pairs) {
   if (!M || key_hi <= key_lo) return;
-  if (RBG_REC_QUAD && quads && !((key_hi - key_lo) & 3))
-    k_records_direct4<<<dim3((key_hi - key_lo + 255) / 256, (M + 31) / 32), 256, 0, st>>>(s, mbase, bias, M, key_lo,
-                                                                                         key_hi, rec);
-  else if (pairs && !(M & 1) && !((key_hi - key_lo) & 1))
+  if (pairs && !(M & 1) && !((key_hi - key_lo) & 1))
     k_records_direct2<<<dim3((key_hi - key_lo + 127) / 128, (M + 63) / 64), 256, 0, st>>>(s, mbase, bias, M, key_lo,
                                                                                           key_hi, rec);
   else
@@ -588,7 +544,6 @@ struct XWin { // one container per lane: the fast-forward window
   uint32_t typ, card, nr;
   uint4 r0, r1;
   uint32_t pairx; // even lanes: |C_lane ⊕ C_lane+1| (set by pair_xor)
-  uint32_t best;  // the lane's longest run, start | (len - 1) << 16 (set by pair_xor)
 };
 // A window's loads form a chain (record -> run list), so they are software-pipelined over three windows:
 // the records of window w+2 and the runs of w+1 are in flight while window w is processed, and every
@@ -597,15 +552,11 @@ struct XWin { // one container per lane: the fast-forward window
 // rotation (W = N) made the compiler load into temporaries and copy them right away, which waited for
 // the loads just issued — every window paid the full memory latency (r03 ISA).
 constexpr int kNextRuns = 768; // u32 offset in the wave's region of the next window's runs (r0 x 64 | r1 x 64)
-#ifndef RBG_XOR_MCOPIES
-#define RBG_XOR_MCOPIES 8 // study builds (A/B of the copy count)
-#endif
-constexpr int kMCopies = RBG_XOR_MCOPIES, kMStride = 33; // touched-word mask copies (lane % copies), strided over distinct banks
+constexpr int kMCopies = 8, kMStride = 33; // touched-word mask copies (lane % copies; the count was A/B-ed), strided over distinct banks
 constexpr int kPcT = 272;                  // u32 offset of pcT (16-B aligned, after the mask copies)
 static_assert(kMCopies * kMStride <= kPcT && kPcT + 256 <= kNextRuns && kNextRuns + 512 <= kXRegion,
               "mask copies, pcT and the next runs inside the region");
 typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void gbl_void_t;
 constexpr int kWaitVm0 = 0x0F70;   // s_waitcnt vmcnt(0)
 constexpr int kWaitLgkm0 = 0xC07F; // s_waitcnt lgkmcnt(0)
 struct XMeta {
@@ -644,7 +595,6 @@ __device__ __forceinline__ XWin xwin_from(const SetView &s, const XMeta &m) {
   w.r1 = p[runs && m.nr > 4u ? 1 : 0];
   w.card = runs_card(w.r0, w.r1, w.nr);
   w.pairx = 0;
-  w.best = 0;
   return w;
 }
 // Round 6: the DMA is issued from inline asm.  Through the builtin the compiler knows that a vmcnt event
@@ -654,16 +604,12 @@ __device__ __forceinline__ XWin xwin_from(const SetView &s, const XMeta &m) {
 // the waitcnt pass, the DMA is waited for only where its slot is read (take_next) or rewritten (exact
 // batches), each by an explicit vmcnt(0); the compiler's own vmcnt waits stay correct (loads return in
 // order, so an extra untracked load only makes them wait longer).
-#ifndef RBG_XOR_DMA_ASM
-#define RBG_XOR_DMA_ASM 1
-#endif
 __device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // the next window's runs, LDS-DMA into nb (lane-linear: r0 of lane l at nb[4l], r1 at nb[256 + 4l])
 __device__ __forceinline__ void stage_next_runs(const SetView &s, const XMeta &m, uint32_t *nb) {
   const bool runs = m.typ == kRun && m.nr && m.nr <= 8u;
   const uint8_t *p = s.payload + (runs ? m.off : 0ull);
   const uint8_t *p1 = p + (runs && m.nr > 4u ? 16 : 0);
-#if RBG_XOR_DMA_ASM
   const uint32_t l0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(lds_void_t *)nb);
   // m0 is reserved: the clobber tells the compiler, which sets m0 nowhere else in this kernel (ISA-checked)
 #pragma clang diagnostic push
@@ -678,10 +624,6 @@ __device__ __forceinline__ void stage_next_runs(const SetView &s, const XMeta &m
                : "v"(p), "v"(p1), "s"(l0)
                : "memory", "m0");
 #pragma clang diagnostic pop
-#else
-  __builtin_amdgcn_global_load_lds((gbl_void_t *)p, (lds_void_t *)nb, 16, 0, 0);
-  __builtin_amdgcn_global_load_lds((gbl_void_t *)p1, (lds_void_t *)(nb + 256), 16, 0, 0);
-#endif
 }
 // the window staged by stage_next_runs (every load of the previous window waited for first)
 __device__ __forceinline__ XWin take_next(const XMeta &m, const uint32_t *nb, int lane) {
@@ -693,7 +635,6 @@ __device__ __forceinline__ XWin take_next(const XMeta &m, const uint32_t *nb, in
   w.r1 = reinterpret_cast<const uint4 *>(nb)[64 + lane];
   w.card = runs_card(w.r0, w.r1, w.nr);
   w.pairx = 0;
-  w.best = 0;
   __builtin_amdgcn_s_waitcnt(kWaitLgkm0); // read before the next DMA overwrites the slot
   return w;
 }
@@ -712,23 +653,17 @@ __device__ __forceinline__ uint32_t longest_run(const XWin &w) {
 }
 __device__ __forceinline__ void pair_xor(XWin &w) {
   const uint32_t best = longest_run(w);
-  w.best = best;
   const uint32_t nbest = dpp<0x130>(best), cb = dpp<0x130>(w.card); // wave_shl:1 — lane l reads lane l+1
   const int sa = (int)(best & 0xFFFF), ea = sa + (int)(best >> 16);
   const int sb = (int)(nbest & 0xFFFF), eb = sb + (int)(nbest >> 16);
   const int inter = w.nr ? max(0, min(ea, eb) - max(sa, sb) + 1) : 0;
   w.pairx = w.card + cb - 2u * (uint32_t)inter;
 }
-// Core-run de-duplication (round 6; PMC profiles/r06/xor): the members of a key usually share a run (config
-// 4: every member holds the key's 1024-value core), so all 64 lanes of a window toggled the same two bits and
-// marked the same U' words — same-address LDS atomics, serialised 64 (toggles) and 8 (marks, one copy per
-// lane & 7) deep: 120 bank-conflict cycles per window, ~70 % of the toggle pass's conflicts (a duplicated
-// toggle pass cost +1.18 ms, +503M conflict cycles).  A wave-uniform candidate run `core` (a lane's longest)
-// is handled once: its toggles by parity (k lanes toggling the same bit is the bit toggled k mod 2 times —
-// one ballot, one atomic by lane 0), its marks once per union stretch (marks are idempotent and U' is only
-// cleared when a stretch starts).  Any run that is not exactly the candidate takes the atomics as before, so
-// results do not depend on the choice.
-constexpr uint32_t kNoCore = 0xFFFFFFFFu;
+// (Round 6, PMC profiles/r06/xor: the members of a key usually share a run — config 4: every member holds the
+// key's 1024-value core — so all 64 lanes of a window toggle the same two bits and mark the same U' words,
+// same-address LDS atomics serialised 64 (toggles) and 8 (marks, one copy per lane & 7) deep: 120 bank-conflict
+// cycles per window, ~70 % of the toggle pass's conflicts.  Handling a wave-uniform candidate core run once,
+// its toggles by parity and its marks once per stretch, measured slower and was deleted: DESIGN.md §7 r06.)
 // the marks of one run word into the touched-word mask copy Mc (1 bit per 64-bit word of the container)
 __device__ __forceinline__ void mark_run(uint32_t *Mc, uint32_t rw) {
   const uint32_t st = rw & 0xFFFF, en = st + (rw >> 16);
@@ -740,34 +675,19 @@ __device__ __forceinline__ void mark_run(uint32_t *Mc, uint32_t rw) {
     for (uint32_t d = d0 + 1; d < d1; ++d) atomicOr(&Mc[d], 0xFFFFFFFFu); // runs over 2048 values
   }
 }
-// the boundary toggles of the active lanes' runs into the toggle image, the candidate's by parity (above);
-// every lane of the wave calls it (ballots)
-__device__ __forceinline__ void toggle_runs_core(const XWin &w, uint32_t *acc, bool act, uint32_t core, int lane) {
-  const uint32_t cs = core == kNoCore ? 0x1FFFFu : (core & 0xFFFFu);
-  const uint32_t ce = core == kNoCore ? 0x3FFFFu : cs + (core >> 16) + 1;
+// the boundary toggles of the active lanes' runs into the toggle image
+__device__ __forceinline__ void toggle_runs(const XWin &w, uint32_t *acc, bool act) {
   const uint32_t rw[8] = {w.r0.x, w.r0.y, w.r0.z, w.r0.w, w.r1.x, w.r1.y, w.r1.z, w.r1.w};
-  bool hs = false, he = false;
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     if (act && (uint32_t)u < w.nr) {
       const uint32_t st = rw[u] & 0xFFFF, e1 = st + (rw[u] >> 16) + 1;
-      const bool ms = st == cs, me = e1 == ce;
-      hs = hs || ms;
-      he = he || me;
-      if (!ms) atomicXor(&acc[st >> 5], 1u << (st & 31));
-      if (!me && e1 < (uint32_t)kSpan) atomicXor(&acc[e1 >> 5], 1u << (e1 & 31));
+      atomicXor(&acc[st >> 5], 1u << (st & 31));
+      if (e1 < (uint32_t)kSpan) atomicXor(&acc[e1 >> 5], 1u << (e1 & 31));
     }
   }
-  const uint64_t bs = __ballot(hs), be = __ballot(he);
-  if (lane == 0) {
-    if (__popcll(bs) & 1) atomicXor(&acc[cs >> 5], 1u << (cs & 31));
-    if ((__popcll(be) & 1) && ce < (uint32_t)kSpan) atomicXor(&acc[ce >> 5], 1u << (ce & 31));
-  }
 }
-#ifndef RBG_XOR_MIN_FAST
-#define RBG_XOR_MIN_FAST 8 // study builds (A/B of the heuristic)
-#endif
-constexpr int kXorMinFast = RBG_XOR_MIN_FAST; // shortest stretch worth a fast-forward (an exact batch costs ~32 stretches' steps)
+constexpr int kXorMinFast = 8; // shortest stretch worth a fast-forward (an A/B-ed heuristic: an exact batch costs ~32 stretches' steps)
 // Union stretches.  The pair bounds above limit an AB stretch to about one window when the members'
 // XOR can reach the accumulator's size (config 4: |C ⊕ C'| ~ 900 per pair, ~29k per window against
 // c ~ 32k), so every window paid a toggle -> word conversion and a re-measure (~600 of ~1100 VALU per
@@ -778,26 +698,7 @@ constexpr int kXorMinFast = RBG_XOR_MIN_FAST; // shortest stretch worth a fast-f
 // per run).  While |P \ U'| >= 32 every step of an AB-typed accumulator is AB(c_j) (c_j >= 32, never
 // empty), so the windows' toggles accumulate in the toggle image with no conversion at all; the stretch
 // closes (one conversion, one re-measure of c) when the next window would push |P \ U'| below 32.
-#ifndef RBG_XOR_UNION_MINC
-#define RBG_XOR_UNION_MINC 1024 // study builds (A/B of the heuristic)
-#endif
-constexpr int kXorUnionMinC = RBG_XOR_UNION_MINC; // try a union stretch only above this c (a heuristic: results do not depend on it)
-#ifndef RBG_STUDY
-#define RBG_STUDY 0 // study builds: per-key stretch counts of three keys (printf)
-#endif
-// Study builds (a per-pass counter split): RBG_XOR_DUP = 1 runs every union window's marks +
-// |P \ U'| check twice, 2 its toggles three times, 3 every union flush twice.  Each repeat leaves the result
-// unchanged (OR marks are idempotent, three XOR toggles equal one, a flush of a zeroed image adds nothing), so
-// the kernel's extra time and counters under a variant are that pass's marginal cost at full occupancy.
-#ifndef RBG_XOR_DUP
-#define RBG_XOR_DUP 0
-#endif
-#ifndef RBG_XOR_CORE_MARKS
-#define RBG_XOR_CORE_MARKS 0 // study builds: 1 de-duplicates the core run's marks only (toggles as before)
-#endif
-#ifndef RBG_XOR_CORE
-#define RBG_XOR_CORE 0 // study builds: 1 de-duplicates the core run's toggles and marks (slower: DESIGN.md §7 r06)
-#endif
+constexpr int kXorUnionMinC = 1024; // try a union stretch only above this c (an A/B-ed heuristic: results do not depend on it)
 
 __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint32_t *__restrict__ rec,
                                                           const uint64_t *__restrict__ seg,
@@ -850,18 +751,6 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
   bool urun = false; // flavour of the pending stretch: Run (every step stays a Run) or AB
   int usum = 0;      // Run flavour: Σ nruns of the pending windows (r_j <= X.r + usum)
   bool wpx = true;   // W.pairx is current
-  uint32_t ccore = kNoCore; // the pending union stretch's candidate core run (wave-uniform), already in U'
-#if RBG_STUDY
-  int tr_u = 0, tr_f = 0, tr_rej = 0, tr_p = 0, tr_pb = 0, tr_e = 0;
-#define RBG_TR(x) x
-  uint64_t tt[6] = {0, 0, 0, 0, 0, 0}, ts = 0; // s_memtime: mark+check, toggles, flush, stretch, exact, advance
-#define RBG_TS() ts = __builtin_amdgcn_s_memtime()
-#define RBG_TA(i) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); tt[i] += t_ - ts; ts = t_; }
-#else
-#define RBG_TR(x)
-#define RBG_TS()
-#define RBG_TA(i)
-#endif
   // the pending windows' XOR into P and (c, r) re-measured: the state is AB(c) (AB flavour) or Run
   auto flush_union = [&]() {
     wave_lds_sync();
@@ -896,7 +785,6 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
     const bool run_in = X.state == kRun && X.rvalid && X.c >= kXorUnionMinC &&
                         X.r + wnr <= 2047 && X.c >= 4 * (X.r + wnr); // |P \ U'| ~ c / 2 after a window
     bool took = false; // the window went into a union stretch
-    RBG_TS();
     if (fastfwd && posw == 0 && (upend || ab_in || run_in)) {
       // ---- union stretch: mark the window's words, then |P \ U'| decides (see "Union stretches" above)
       const bool mem = (uint32_t)lane < wlen;
@@ -908,20 +796,14 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
         for (int k = 0; k < 8; ++k)
           reinterpret_cast<uint16_t *>(pcT)[64 * k + lane] =
               (uint16_t)(__popcll(Pw[2 * k]) | (__popcll(Pw[2 * k + 1]) << 8));
-        ccore = readlane(longest_run(W), 0); // lane 0 is a member of every union window (posw == 0)
         wave_lds_sync();
-        if (lane == 0 && (RBG_XOR_CORE || RBG_XOR_CORE_MARKS)) mark_run(M, ccore); // once for the stretch (copy 0)
       }
-      const uint32_t mcore = RBG_XOR_CORE ? ccore : kNoCore;
-      const uint32_t mkcore = RBG_XOR_CORE || RBG_XOR_CORE_MARKS ? ccore : kNoCore;
-      int L = 0;
-      for (int rep = 0; rep < (RBG_XOR_DUP == 1 ? 2 : 1); ++rep) {
       if (mem) {
         const uint32_t rw[8] = {W.r0.x, W.r0.y, W.r0.z, W.r0.w, W.r1.x, W.r1.y, W.r1.z, W.r1.w};
         uint32_t *Mc = M + kMStride * (lane & (kMCopies - 1));
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-          if ((uint32_t)u < W.nr && rw[u] != mkcore) mark_run(Mc, rw[u]); // the candidate is in U' already
+          if ((uint32_t)u < W.nr) mark_run(Mc, rw[u]);
       }
       wave_lds_sync();
       // |P \ U'|: lane l sums the popcounts of words 16 l .. 16 l + 15 not in U'
@@ -942,33 +824,22 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
         }
         ls = (ls & 0xFFFFu) + (ls >> 16);
       }
-      L = (int)wave_sum_u32(ls);
-      if (RBG_XOR_DUP == 1) wave_lds_sync();
-      }
-      RBG_TA(0);
+      const int L = (int)wave_sum_u32(ls);
       const int rub = X.r + usum + wnr; // >= every r_j of the stretch (Run flavour)
       if (urun ? (2 + 4 * rub <= min(kBitmapBytes, 2 * L + 2)) : L >= kRunArrayThreshold) {
         usum += wnr;
-        for (int rep = 0; rep < (RBG_XOR_DUP == 2 ? 3 : 1); ++rep) toggle_runs_core(W, acc, mem, mcore, lane);
+        toggle_runs(W, acc, mem);
         if (mem) X.inb += 4u * W.nr + 2u + 16u;
         ++upend;
-        RBG_TR(++tr_u);
-        RBG_TA(1);
         base += wlen;
         took = true; // on to the one shared window advance below
       }
       // this window would let U' cover too much of P: close the stretch before it and take the window
       // again as the first of a fresh stretch (U' then holds its words alone); a window refused as
       // the first of a stretch goes to the per-window rules
-      else {
-        RBG_TR(++tr_rej);
-        if (upend) {
-          RBG_TR(++tr_f);
-          flush_union();
-          if (RBG_XOR_DUP == 3) flush_union();
-          RBG_TA(2);
-          continue;
-        }
+      else if (upend) {
+        flush_union();
+        continue;
       }
     }
     if (!took) { // the per-window rules: a pair-bounded stretch, or an exact batch
@@ -1001,7 +872,7 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
       const uint32_t B = fastfwd ? min(~okm ? (uint32_t)__builtin_ctzll(~okm) : 64u, wlen - posw) : 0u;
       if (B >= kXorMinFast || (B >= 1 && posw + B == wlen)) {
         const bool act = (uint32_t)lane >= posw && (uint32_t)lane < posw + B;
-        toggle_runs_core(W, acc, act, RBG_XOR_CORE ? readlane(W.best, (int)posw) : kNoCore, lane);
+        toggle_runs(W, acc, act);
         if (act) X.inb += 4u * W.nr + 2u + 16u;
         wave_lds_sync();
         uint64_t t[kW];
@@ -1020,8 +891,6 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
         X.rvalid = mode == 2;
         X.state = mode == 1 ? type_ab(cc) : kRun;
         base += B;
-        RBG_TR(++tr_p; tr_pb += B);
-        RBG_TA(3);
       } else {
         if (!X.rvalid) {
           int cc, rr;
@@ -1041,12 +910,9 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
         lds_zero(acc, lane);
         stage_next_runs(s, Nm, nbuf); // the batch overwrote them: again
         base += kXB;
-        RBG_TR(++tr_e);
-        RBG_TA(4);
       }
     }
     wave_lds_sync();
-    RBG_TS();
     if (base >= wbase + 64 && base < hi) {
       wbase += 64;
       W = take_next(Nm, nbuf, lane);
@@ -1055,7 +921,6 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
       NN = rec_at(wbase + 128 + lane);
       wpx = false;
     }
-    RBG_TA(5);
   }
   wait_vm0(); // no DMA into this block's LDS outlives the wave
   if (fail_route) {
@@ -1063,15 +928,8 @@ __global__ __launch_bounds__(256, 3) void k_wide_runs_xor(SetView s, const uint3
     return;
   }
   if (upend) {
-    RBG_TR(++tr_f);
     flush_union();
   }
-#if RBG_STUDY
-  if (lane == 0 && (q == 1000 || q == 30000 || q == 65000))
-    printf("xor trace key %u: union windows %d flushes %d refused %d | per-window stretches %d (members %d) | exact %d | c %d state %d"
-           " | cycles mark %lu toggles %lu flush %lu stretch %lu exact %lu advance %lu\n",
-           q, tr_u, tr_f, tr_rej, tr_p, tr_pb, tr_e, X.c, X.state, tt[0], tt[1], tt[2], tt[3], tt[4], tt[5]);
-#endif
   // ---- result
   uint8_t *dst = out + (uint64_t)q * kBitmapBytes;
   const int ty = X.state == 3 ? (int)kEmpty : X.state;
@@ -1115,10 +973,7 @@ void launch_wide_runs_xor(const SetView &s, const uint32_t *cid, const uint64_t 
     k_records_gather<<<(unsigned)std::min<uint64_t>((xr.n + 255) / 256, 65536), 256, 0, st>>>(xr.mrec, cid, seg,
                                                                                            xr.rec);
   }
-#ifndef RBG_XOR_LDS_PAD
-#define RBG_XOR_LDS_PAD 0 // study: dynamic LDS a block reserves without using it (8192: 2 waves per SIMD instead of 3)
-#endif
-  k_wide_runs_xor<<<(nk + 3) / 4, 256, RBG_XOR_LDS_PAD, st>>>(s, xr.rec, seg, klist, nk, out, wo, route, stats, fastfwd);
+  k_wide_runs_xor<<<(nk + 3) / 4, 256, 0, st>>>(s, xr.rec, seg, klist, nk, out, wo, route, stats, fastfwd);
 }
 
 // this file's code object, loaded at context creation (rbgpu_open, context.hip)

@@ -3,8 +3,8 @@ known before the OR — a Bitmap, or the full Run (BitmapContainer.or, BitmapCon
 RunContainer.or(Bitmap)), a Bitmap even when full for BitmapContainer.ior(ArrayContainer) (:749-766).  Every
 ordered pair of a container zoo (large, near-full and full Bitmaps; Arrays that fill a gap; Runs of <= 2047
 and of 32768 runs, the > 8 KiB staging path), static, in place and cardinality-only, byte-exact against the
-oracle.  The default build keeps these pairs on the register path; RBG_OR_BITS=1 builds (a study: slower) send
-them to the copy + filter kernel — the same bytes either way."""
+oracle.  These pairs run on the register path; a round-6 variant that sent them to the copy + filter kernel
+(measured slower and deleted) had to give the same bytes."""
 import numpy as np
 import pytest
 

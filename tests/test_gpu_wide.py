@@ -379,7 +379,7 @@ def test_xor_fastforward_threshold_regimes(ctx, oracle):
 
 
 def test_xor_union_stretches(ctx, oracle):
-    """naive_xor union stretches (wide_xor.hip, RBG_XOR_UNION): whole windows of 64 members are
+    """naive_xor union stretches (wide_xor.hip, "Union stretches"): whole windows of 64 members are
     XORed without re-measuring while |P \\ U'| >= 32 (U' = the windows' runs rounded out to 64-bit
     words); chains of 1100 members so stretches span many windows and close on that bound:
       key 0  config-4 shape: stretches of several windows, closed as U' covers the key;
