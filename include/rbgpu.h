@@ -428,6 +428,57 @@ int rbgpu_bsi_values_device(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_se
  * Either output may be NULL.  rb_stats: kernel k_bsi_get, tasks = n. */
 int rbgpu_bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n,
                          uint64_t *values, uint8_t *exists);
+/* ---- BSI arithmetic: add, merge, minValue / maxValue (bsi_arith.hip) --------------------------------------------
+ * `a`, `b`, `bsi`: BSI sets as above (0..64 slices, then ebM; column ids 32-bit, values unsigned 64-bit).  Inputs are
+ * never modified, results are new sets, and slices within ebM is the caller's invariant (not checked).  A NULL set, a
+ * set of 0 or more than 65 bitmaps, a set of another context or an unknown flag bit gives RB_EINVAL on the host,
+ * before any launch.
+ *
+ * Roaring64BitmapSliceIndex.add(otherBsi) (longlong/Roaring64BitmapSliceIndex.java:64-93; RoaringBitmapSliceIndex.java:
+ * 66-95; buffer/MutableBitSliceIndex.java:121-215): value[c] = a[c] + b[c] over the union of the columns (a column of
+ * ebM may hold 0).  b's ebM empty: a clone of a, its bitmap count kept (the reference returns early).  Otherwise
+ * n = max(na, nb) slices, n + 1 exactly when the carry out of slice n - 1 is not empty (grow is only called on a
+ * non-empty carry), then ebM = a.ebM after or(b.ebM) in place (the types of rbgpu_pairwise_inplace(RB_OR)).  n == 64
+ * with a carry out of slice 63: RB_EINVAL, nothing created (the reference would grow a 65th slice no long reads back).
+ * Container types of the slices, per high key, with c_j the carry into slice j (c_0 = 0, c_{j+1} = maj(a_j, b_j, c_j)):
+ *   b_j absent, c_j = 0      a_j's container copied as it is (a Run included); absent if absent
+ *   a_j absent, c_j = 0      b_j's container copied as it is (the xor inserts a clone)
+ *   anything else            the bits a_j ^ b_j ^ c_j: an Array up to 4096 members, a Bitmap above, dropped when empty
+ * which is what the reference's chain of and / in-place xor per digit (addDigit) leaves wherever it touches no Run
+ * container.  A touched Run's result type depends on the chain's history (RunContainer.xor looks at the operand's type
+ * and size, Run ^ Run goes through toEfficientContainer), so a call in which some high key holds slice containers of
+ * both indexes and a Run among them takes the chain itself, over rbgpu_pairwise(RB_AND) and
+ * rbgpu_pairwise_inplace(RB_XOR): slow, and exact for every container class by construction.  RB_BSI_ADD_CHAIN forces
+ * the chain.  64-bit quirk: Roaring64Bitmap.xor keeps a container that ends empty (Roaring64Bitmap.java:392-411),
+ * RoaringBitmap.xor drops it (RoaringBitmap.java:3296-3348); a device set cannot hold one, so the result is
+ * RoaringBitmapSliceIndex.add's: such a container is absent, and the slice bitmap stays in the count even with no
+ * container left.  *min_value / *max_value (either may be NULL): minValue() / maxValue() of the result, which the
+ * reference stores after add.
+ * rb_stats, fused path: kernel spans k_bsi_add<measure> and k_bsi_add<emit> (main_kernel is one of them), tasks = high
+ * keys walked, input_bytes = payload + 16 B of every slice container read (copied or combined) on both sides,
+ * output_bytes = payload + 16 B per result slice container; ebM's union is a pairwise call made before them and
+ * min / max a k_bsi_minmax pass after them, outside these counters.  On the chain rb_stats is the last pairwise
+ * call's, so main_kernel names a pairwise kernel.  Two calls name no kernel at all (n_kernels = 0, main_kernel empty,
+ * no bytes counted): the clone for an empty b (rbgpu_bsi_merge's too; result_containers = the clone's), and a fused
+ * call in which neither index holds a slice container (every value 0: the result is empty slices and ebM's union). */
+enum rb_bsi_add_flags { RB_BSI_ADD_CHAIN = 1 };
+int rbgpu_bsi_add(rbgpu_ctx *ctx, const rbgpu_set *a, const rbgpu_set *b, uint32_t flags, rbgpu_set **out,
+                  uint64_t *min_value, uint64_t *max_value);
+/* Roaring64BitmapSliceIndex.merge(otherBsi) (:357-383, "designed for distributed computing"): the union of two indexes
+ * over disjoint columns.  b's ebM empty: a clone of a.  Intersecting ebMs: RB_EINVAL (the reference's
+ * IllegalArgumentException), nothing created.  Otherwise max(na, nb) slices, each the static or of the two sides'
+ * slices (a missing slice stands in as an empty bitmap), followed by runOptimize() when flags holds
+ * RB_BUILD_RUN_OPTIMIZE (a binding passes this.runOptimized || other.runOptimized); ebM is the in-place or and is not
+ * run-optimised.  Every step is one container op of rbgpu_pairwise / rbgpu_pairwise_inplace / rbgpu_set_run_optimize,
+ * so the types are exact for every container class.  minValue / maxValue are the min / max of the two indexes' fields
+ * (the binding's).  rb_stats: the last of those calls'. */
+int rbgpu_bsi_merge(rbgpu_ctx *ctx, const rbgpu_set *a, const rbgpu_set *b, uint32_t flags, rbgpu_set **out);
+/* minValue() / maxValue() (:95-125): the smallest and the largest value over ebM's columns, 0 and 0 for an empty ebM.
+ * True unsigned 64-bit values; the reference's valueAt accumulates `1 << i` in an int and agrees for bitCount <= 31
+ * (the convention of rbgpu_bsi_sum and rbgpu_bsi_values).  One wave per high key of ebM descends the slices once for
+ * both.  rb_stats: kernel k_bsi_minmax, tasks = keys of ebM walked, input_bytes = payload + 16 B of ebM's and the
+ * slices' containers at those keys. */
+int rbgpu_bsi_min_max(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint64_t *min_value, uint64_t *max_value);
 /* RoaringBitmap.runOptimize (RoaringBitmap.java:2764-2775) of every bitmap of `in` into a new set:
  * each Array / Bitmap container becomes a Run when that is strictly smaller, each Run goes through
  * toEfficientContainer (ArrayContainer.java:1085-1099, BitmapContainer.java:1227-1246,

@@ -18,9 +18,10 @@ from ._lib import BUFFER_NAIVE_OR, BUFFER_PQ_OR, BUFFER_PQ_OR_ITER, BUFFER_PQ_XO
 from .engine import Comm, DeviceSet64
 from ._lib import RB64_BITMAP, RB64_NAVIGABLE
 from ._lib import RANGE_ADD, RANGE_FLIP, RANGE_REMOVE
+from ._lib import BSI_ADD_CHAIN
 
 __all__ = [
-    "RANGE_ADD", "RANGE_REMOVE", "RANGE_FLIP",
+    "RANGE_ADD", "RANGE_REMOVE", "RANGE_FLIP", "BSI_ADD_CHAIN",
     "AND", "OR", "XOR", "ANDNOT", "ARRAY", "BITMAP", "RUN",
     "FAST_OR", "FAST_AND", "WORKSHY_AND", "NAIVE_AND", "FAST_XOR", "PAR_OR", "PAR_XOR", "NAIVE_AND_ITER",
     "HORIZONTAL_OR", "HORIZONTAL_XOR", "PQ_OR", "PQ_XOR", "Comm",

@@ -27,6 +27,7 @@ BSI_EQ, BSI_NEQ, BSI_LE, BSI_LT, BSI_GE, BSI_GT, BSI_RANGE = range(7)  # BitmapS
 RANGE_ADD, RANGE_REMOVE, RANGE_FLIP = range(3)  # rb_range_op
 BUILD_RUN_OPTIMIZE = 1  # rb_build_flags
 BUILD_TILE = 1024       # RB_BUILD_TILE: elements per block of the value build's container discovery
+BSI_ADD_CHAIN = 1       # rb_bsi_add_flags: the reference's per-digit chain instead of the fused pass
 
 
 class RbSoa(C.Structure):
@@ -184,6 +185,9 @@ SIGNATURES = {
     "rbgpu_bsi_values_device": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                           _U64P]),
     "rbgpu_bsi_get_values": (C.c_int, [_P, _P, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rbgpu_bsi_add": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_P), _U64P, _U64P]),
+    "rbgpu_bsi_merge": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_P)]),
+    "rbgpu_bsi_min_max": (C.c_int, [_P, _P, _U64P, _U64P]),
     "rbgpu_generate_bsi_keys": (C.c_int, [_P, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                           C.POINTER(_P)]),
     "rbgpu_set_extract": (C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(_P)]),

@@ -6,6 +6,7 @@
     getExistenceBitmap / bitCount / runOptimize          :141-168
     sum / topK                                            :559-594
     getValue / valueExist / transpose                     :177-184, 284-286, 596-601
+    add / merge / minValue / maxValue                     :64-93, 357-383, 95-125
     toPairList                                            buffer/BitSliceIndexBase.java:534-549
 
 The slices and the existence bitmap live in HBM as one DeviceSet (slices bA[0..n), then ebM) and a
@@ -55,8 +56,14 @@ class Roaring64BitmapSliceIndex:
             self.setValue(c, v)
 
     @classmethod
-    def from_device(cls, dset: DeviceSet, min_value: int, max_value: int) -> "Roaring64BitmapSliceIndex":
-        """Wrap a device-resident BSI (slices then ebM), e.g. rbgpu_generate_bsi's."""
+    def from_device(cls, dset: DeviceSet, min_value: Optional[int] = None,
+                    max_value: Optional[int] = None) -> "Roaring64BitmapSliceIndex":
+        """Wrap a device-resident BSI (slices then ebM), e.g. rbgpu_generate_bsi's.  min_value / max_value left
+        out: computed on the device (rbgpu_bsi_min_max) — compare short-circuits on them, so they must be true."""
+        if min_value is None or max_value is None:
+            lo, hi = dset.ctx.bsi_min_max(dset)
+            min_value = lo if min_value is None else min_value
+            max_value = hi if max_value is None else max_value
         b = cls()
         b._dev, b.minValue, b.maxValue, b._nbits = dset, min_value, max_value, len(dset) - 1
         b._cols = None
@@ -73,6 +80,34 @@ class Roaring64BitmapSliceIndex:
     def runOptimize(self) -> None:
         self._run_optimized = True
         self._dev = None
+
+    # ---- arithmetic (Roaring64BitmapSliceIndex.java:64-93, 357-383): both leave the index device-resident, as
+    # after from_device
+    def _adopt(self, dset: DeviceSet, min_value: int, max_value: int) -> None:
+        self._dev, self._cols, self._nbits = dset, None, len(dset) - 1
+        self.minValue, self.maxValue = min_value, max_value
+
+    def add(self, other: Optional["Roaring64BitmapSliceIndex"]) -> None:
+        """add(otherBsi): value[c] += other[c] over the union of the columns, on the device (rbgpu_bsi_add);
+        minValue / maxValue are recomputed, as the reference does.  None or an empty other index changes nothing."""
+        if other is None or other._no_rows():
+            return
+        d, o = self._device(), other._device()
+        self._adopt(*d.ctx.bsi_add(d, o))
+
+    def merge(self, other: Optional["Roaring64BitmapSliceIndex"]) -> None:
+        """merge(otherBsi): the union with an index over disjoint columns (rbgpu_bsi_merge); the slices are
+        run-optimised when either index was, minValue / maxValue are the min / max of the two fields, like the
+        reference.  Common columns raise ValueError (InvalidArgument)."""
+        if other is None or other._no_rows():
+            return
+        d, o = self._device(), other._device()
+        if int(o.cardinalities()[-1]) == 0:
+            return
+        ro = self._run_optimized or other._run_optimized
+        res = d.ctx.bsi_merge(d, o, run_optimize=ro)
+        self._adopt(res, min(self.minValue, other.minValue), max(self.maxValue, other.maxValue))
+        self._run_optimized = ro
 
     def bitCount(self) -> int:
         return self._nbits

@@ -604,7 +604,7 @@ static int min_max_shortcut(int op, uint64_t a, uint64_t b, uint64_t mn, uint64_
 // The set's key -> container tables (rows 0..nbits: its slices and ebM; row nbits + 1: a call's foundSet)
 // and ebM's key list, built on the set's first compare and kept with it (sets are immutable): the device
 // time and bytes are the set's setup part 3 (rbgpu_set_setup_parts).
-static int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *cs, uint32_t nbits) {
+int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *cs, uint32_t nbits) {
   rbgpu_set *s = const_cast<rbgpu_set *>(cs);
   if (s->bsi_table) return RB_OK;
   int rc = ensure_h_begin(s);

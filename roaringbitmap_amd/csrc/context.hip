@@ -243,7 +243,7 @@ int rbgpu_open(int device, rbgpu_ctx **out) {
   // the first launch of one of its kernels (~1 ms each), which otherwise lands in that call's time and in a
   // set's first-use setup (rbgpu_set_setup_parts)
   for (auto w : {warm_pairwise, warm_scan, warm_wide, warm_wide_runs, warm_wide_xor, warm_bsi, warm_codec, warm_setops,
-                 warm_generate, warm_values, warm_build, warm_range})
+                 warm_generate, warm_values, warm_build, warm_range, warm_bsi_arith})
     w(c->stream);
   if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
     rbgpu_close(c);

@@ -420,6 +420,14 @@ int bsi_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const rbgpu_set *found, uin
                uint32_t *cols, uint64_t *vals, uint64_t cap, uint64_t *count, bool host_dst);
 int bsi_get_values(rbgpu_ctx *ctx, const rbgpu_set *bsi, const uint32_t *columns, uint64_t n, uint64_t *values,
                    uint8_t *exists);
+// bsi.hip: the set's key -> container tables (rows 0..nbits: its slices and ebM) and ebM's key list (rbgpu_set::
+// bsi_table / bsi_klist / bsi_nk), built on first use and kept with the set
+int ensure_bsi_tables(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint32_t nbits);
+// bsi_arith.hip: Roaring64BitmapSliceIndex.add / merge / minValue + maxValue over BSI sets (checked by the entry points)
+int bsi_add(rbgpu_ctx *ctx, const rbgpu_set *a, const rbgpu_set *b, uint32_t flags, rbgpu_set **out, uint64_t *min_value,
+            uint64_t *max_value);
+int bsi_merge(rbgpu_ctx *ctx, const rbgpu_set *a, const rbgpu_set *b, uint32_t flags, rbgpu_set **out);
+int bsi_min_max(rbgpu_ctx *ctx, const rbgpu_set *bsi, uint64_t *min_value, uint64_t *max_value, bool with_stats);
 // values.hip, the read-out of plain sets: the members of bitmaps [first, first + count) back to back (host_dst:
 // dst is host memory, else device memory; null: the offsets only), and batched contains / rank / select (host
 // arrays; `bitmap` may be null: bitmap 0)

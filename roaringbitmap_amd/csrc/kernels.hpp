@@ -15,6 +15,7 @@ void scan_exclusive_multi(const uint64_t *const *in, uint64_t *const *out, int k
 void launch_noop(hipStream_t st);
 // one empty launch per source file: HIP loads a file's code object at the first launch of any of its kernels
 void warm_bsi(hipStream_t st);
+void warm_bsi_arith(hipStream_t st);
 void warm_build(hipStream_t st);
 void warm_codec(hipStream_t st);
 void warm_generate(hipStream_t st);

@@ -763,6 +763,30 @@ class Context:
                                              vals.ctypes.data if len(c) else None, ex.ctypes.data if len(c) else None))
         return vals, ex.astype(bool)
 
+    def bsi_add(self, a: DeviceSet, b: DeviceSet, chain: bool = False) -> Tuple[DeviceSet, int, int]:
+        """Roaring64BitmapSliceIndex.add over two device BSIs: (the sum as a new set, its minValue, its maxValue);
+        the inputs stay unchanged (rbgpu_bsi_add).  One fused pass per high key unless a touched container is a
+        Run — then, or with chain=True, the reference's per-digit chain over the pairwise calls.  A sum that needs
+        a 65th slice raises InvalidArgument and creates nothing."""
+        out, lo, hi = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        L.check(L.lib().rbgpu_bsi_add(self.h, a.h, b.h, L.BSI_ADD_CHAIN if chain else 0, C.byref(out), C.byref(lo),
+                                      C.byref(hi)))
+        return DeviceSet(self, out.value), int(lo.value), int(hi.value)
+
+    def bsi_merge(self, a: DeviceSet, b: DeviceSet, run_optimize: bool = False) -> DeviceSet:
+        """Roaring64BitmapSliceIndex.merge: the union of two device BSIs over disjoint columns as a new set; the
+        slices are run-optimised when asked, ebM never (rbgpu_bsi_merge).  Intersecting existence bitmaps raise
+        InvalidArgument."""
+        out = C.c_void_p()
+        L.check(L.lib().rbgpu_bsi_merge(self.h, a.h, b.h, L.BUILD_RUN_OPTIMIZE if run_optimize else 0, C.byref(out)))
+        return DeviceSet(self, out.value)
+
+    def bsi_min_max(self, bsi: DeviceSet) -> Tuple[int, int]:
+        """(minValue(), maxValue()) of a device BSI, (0, 0) for an empty one (rbgpu_bsi_min_max)."""
+        lo, hi = C.c_uint64(), C.c_uint64()
+        L.check(L.lib().rbgpu_bsi_min_max(self.h, bsi.h, C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
     def generate_bsi(self, nslices: int, nrows: int, seed: int = 42, key_range=None) -> DeviceSet:
         """The synthetic BSI of SURVEY §8d config 5, or its [lo, hi) key-range shard."""
         a = C.c_void_p()
